@@ -18,6 +18,12 @@ friction decay D <- D(1 - 1/2600) per tick (rt.py:125-130), xref from ConstantSp
 packaged ETHZ raceline library.  All tick inputs are resident in HBM before timing.
 
 value = (N_total * C * H + N_total) / (ms_per_step / 1e3)  [model-rollout-steps / s].
+
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) sets up, warms up, times the K ticks,
+writes the last tick's outputs if --dump-outputs DIR is given, and prints the result line.
+Everything else the benchmark measures (the per-plan() call latency, the C=64 / latency /
+config 3 / config 5 / controller / NLP extras, the CPU baselines) runs only with --full; the
+--no-* options then leave single legs of it out.
 """
 import argparse
 import ctypes
@@ -79,12 +85,44 @@ def parse():
                     help="friction change of the tick inputs (default: gradual on ETHZ, sudden on "
                          "ETHZMobil, BASELINE configs 2/3)")
     ap.add_argument("--ticks", type=int, default=64, help="distinct resident tick inputs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline: the per-plan() call "
+                         "latency, the extras (C=64, latencies, configs 3 and 5, controller, NLP solve) and "
+                         "the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed tick computed (the merged plan record's fields and the "
+                         "bank's error window) as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C=64 and latency extras")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C=64 and latency extras")
     ap.add_argument("--no-timing", action="store_true", help="no per-kernel HIP events")
-    ap.add_argument("--no-call-latency", action="store_true", help="skip the per-plan() H2D+tick+D2H latency")
+    ap.add_argument("--no-call-latency", action="store_true",
+                    help="with --full: skip the per-plan() H2D+tick+D2H latency")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, sb):
+    """--dump-outputs: what a caller of the timed path receives from its last tick, as
+    <path>/<name>.npy (float64; the indices and counts are exact in it): every field of the
+    merged plan record in sb.h_merged (fetched by the caller) and the tick's other product, this
+    rank's error window [N, W] (newest in the last column) — its rows sampled by a fixed seed
+    when the whole would pass DUMP_MAX_BYTES."""
+    from llampc import _native as nat
+    os.makedirs(path, exist_ok=True)
+    rec = nat.plan_out_to_dict(nat.PlanOut.from_buffer_copy(sb.h_merged.numpy().tobytes()))
+    for k, v in rec.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    win = sb.bank.window()
+    budget = DUMP_MAX_BYTES - (1 << 20)                 # the record's files are a few hundred bytes each
+    rows = max(1, budget // (8 * win.shape[1] + 8))
+    if win.shape[0] > rows:
+        idx = np.sort(np.random.RandomState(0).choice(win.shape[0], size=rows, replace=False))
+        np.save(os.path.join(path, "error_window_rows.npy"), idx.astype(np.float64))
+        win = win[idx]
+    np.save(os.path.join(path, "error_window.npy"), np.ascontiguousarray(win, dtype=np.float64))
 
 
 def make_ticks(args, T, seed=0):
@@ -415,13 +453,15 @@ def main():
         plan_ms = max_over_ranks(plan_ms)
 
     merged = sb.fetch(stream)          # result of the last tick (all ranks identical)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sb)
 
     # SURVEY §8(d)'s per-plan() wall time: the same tick with its inputs coming from host
     # memory and its record going back (every rank; the exchange included when world > 1)
-    call = None if args.no_call_latency else plan_call_latency(args, sb, stream, ticks, world)
+    call = plan_call_latency(args, sb, stream, ticks, world) if args.full and not args.no_call_latency else None
 
     extra = {}
-    if not args.no_extra:              # every rank: the C=64 extra ticks run the collective
+    if args.full and not args.no_extra:    # every rank: the C=64 extra ticks run the collective
         extra = extras(args, sb, stream, world, rank)
 
     if rank == 0:
@@ -455,8 +495,8 @@ def main():
                        "transport": sb.transport, "transport_fallback": sb.fallback_reason},
             "value_basis": "resident inputs: ms_per_step = wall time per tick of llampc_plan_device (ONE launch"
                            + (" + the exchange" if sb.exchange else "") + ") on tick inputs already in HBM, "
-                           "K ticks back to back; plan_call_us is the same tick with H2D of its inputs and "
-                           "D2H of its record, timed alone",
+                           "K ticks back to back; plan_call_us (--full) is the same tick with H2D of its "
+                           "inputs and D2H of its record, timed alone",
             "plan_call_us": call,
             "roofline": roof,
             "valu": {"bound": "fp64-valu", "achieved_gflops": valu_gf, "peak_tflops": FP64_VALU_PEAK_TFLOPS,
@@ -485,7 +525,7 @@ def main():
             "cpu_baseline": None,
         }
         line.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     sb.close()

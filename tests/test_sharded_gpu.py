@@ -157,7 +157,7 @@ def test_bench_spawns_its_own_ranks(exchange):
     for the whole job — rehearsed on one GPU (LLAMPC_SAME_DEVICE=1, gloo for the host-side
     collectives; the records travel through the peer mailboxes, or with LLAMPC_EXCHANGE=host
     through the process group: the transport a node without peer access falls back to) —
-    extras included: C = 64 ticks, BASELINE config 5 (two tracks) sharded over both ranks and
+    extras included (--full): C = 64 ticks, BASELINE config 5 (two tracks) sharded over both ranks and
     the sharded controller."""
     import json
     import subprocess
@@ -166,7 +166,7 @@ def test_bench_spawns_its_own_ranks(exchange):
     env.update(LLAMPC_DIST_BACKEND="gloo", LLAMPC_SAME_DEVICE="1", LLAMPC_EXCHANGE=exchange)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "40",
                         "--warmup", "5", "--ticks", "4", "--n-per-gpu", "2000",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -7,9 +7,9 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp; mkdir -p gpurun_out/mul
 O=gpurun_out/multi
 LLAMPC_DIST_BACKEND=gloo LLAMPC_SAME_DEVICE=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 \
   --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29583 bench.py --gpus 2 --steps 500 --warmup 20 \
-  --no-cpu-baseline > $O/rehearse2.json 2> $O/rehearse2.err && \
+  --full --no-cpu-baseline > $O/rehearse2.json 2> $O/rehearse2.err && \
 LLAMPC_FORCE_EXCHANGE=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-  --master-addr 127.0.0.1 --master-port 29584 bench.py --gpus 1 --steps 1000 --warmup 20 --no-cpu-baseline \
+  --master-addr 127.0.0.1 --master-port 29584 bench.py --gpus 1 --steps 1000 --warmup 20 --full --no-cpu-baseline \
   > $O/force1.json 2> $O/force1.err
 rc=$?
 for f in $O/rehearse2 $O/force1; do
