@@ -206,12 +206,24 @@ int llampc_lookback(llampc_bank* bank, const double* x_prev, const double* u_pre
                     double* topk_val, int32_t* window_count);
 
 /* ---- look-ahead (host pointers) ------------------------------------------------- */
-/* cost_out [n][C] and best_cand_out [n] may be NULL. */
+/* cost_out [n][C] and best_cand_out [n] may be NULL.  A candidate that is infeasible under
+ * cost.enforce_bounds costs +inf; the argmins treat NaN as +inf and break ties towards the
+ * lower index, so when every candidate of a model is infeasible its best candidate is 0 with
+ * cost +inf, and when every (model, candidate) pair is, best_model = best_cand = 0 and
+ * best_cost = +inf (np.argmin over all-inf). */
 int llampc_lookahead(llampc_bank* bank, const double* x0, const double* U, int32_t C,
                      int32_t H, const double* xref, const double* uprev,
                      const llampc_cost* cost, double Ts, int32_t integrator,
                      double* cost_out, int32_t* best_cand_out, int64_t* best_model,
                      int32_t* best_cand, double* best_cost);
+
+/* The look-ahead kernel variant a launch of n models, C candidates, H steps takes with the
+ * shared (GIVEN) xref — host only, no device needed (for tests that mean to run one variant):
+ * out = {lpm (lanes per rollout: 4, 2 or 1; honours the LLAMPC_LPM override exactly as the
+ * launch does), G (lanes per model), cpl (candidates per lane), stage (1: the candidate
+ * inputs are staged in LDS)}.  share = llampc_bank_set_concurrency's banks (1 by default). */
+int llampc_plan_variant(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share,
+                        int32_t out[4]);
 
 /* Attach (replace) the raceline library used by LLAMPC_XREF_RACELINE: natural cubic
  * splines over the arc length (pycubicspline.py:17-182, track.py:52-83): knots [n]

@@ -2539,6 +2539,22 @@ extern "C" int llampc_integrate_batch(const double* x0, const double* u, int64_t
   return LLAMPC_OK;
 }
 
+// The variant launch_plan picks for the given-xref layout, from the same functions it calls.
+extern "C" int llampc_plan_variant(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share,
+                                   int32_t out[4]) {
+  if (!out) return fail(LLAMPC_E_ARG, "NULL argument");
+  if (n < 1 || C < 1 || H < 1 || integrator < LLAMPC_RK4 || integrator > LLAMPC_RK6)
+    return fail(LLAMPC_E_ARG, "n %lld, C %d, H %d, integrator %d", (long long)n, C, H, integrator);
+  const int G = lookahead_group(C);
+  bool stage = false;
+  (void)lookahead_lds_bytes(C, H, &stage);
+  out[0] = lookahead_lpm(n, C, integrator, share);
+  out[1] = G;
+  out[2] = (C + G - 1) / G;
+  out[3] = stage ? 1 : 0;
+  return LLAMPC_OK;
+}
+
 extern "C" int llampc_math_batch(int32_t fn, const double* a, const double* b, int64_t n,
                                  double* out, int32_t device) {
   if (!a || !out || ((fn == LLAMPC_MATH_ATAN2_XPOS || fn == LLAMPC_MATH_ATAN2_FAST ||

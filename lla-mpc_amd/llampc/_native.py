@@ -126,6 +126,8 @@ _SIGNATURES = {
                                    C.POINTER(Cost), C.c_double, C.c_int32, _dp,
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_int32), _dp]),
+    "llampc_plan_variant": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(C.c_int32)]),
     "llampc_plan": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), C.POINTER(PlanOut), _dp, _dp, _dp]),
     "llampc_plan_device": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -227,6 +229,15 @@ def device_count() -> int:
     n = C.c_int32(0)
     rc = load().llampc_device_count(C.byref(n))
     return n.value if rc == 0 else 0
+
+
+def plan_variant(n: int, C_: int, H: int, integrator="rk4", share: int = 1) -> dict:
+    """The look-ahead variant a given-xref launch takes (llampc_plan_variant; host only, reads
+    LLAMPC_LPM as the launch does): {lpm, G, cpl, stage}."""
+    out = (C.c_int32 * 4)()
+    integ = INTEGRATORS[integrator] if isinstance(integrator, str) else int(integrator)
+    check(load().llampc_plan_variant(int(n), int(C_), int(H), integ, int(share), out))
+    return dict(lpm=out[0], G=out[1], cpl=out[2], stage=bool(out[3]))
 
 
 def dptr(a: np.ndarray | None):

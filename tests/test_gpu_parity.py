@@ -6,7 +6,13 @@ shape is 1e-10, profiles/r05/accuracy_lean.txt; north star bound: 1e-5); indices
 (tie-tolerant only where stated).  Ill-conditioned rollouts (a one-ulp change of x0 moves the
 cost visibly in the oracle itself) are held to their core-error bound — the lean cores'
 measured errors propagated through the oracle's rollout (conftest.core_error_bound) — in
-tests/test_configs_gpu.py, tests/test_ctl_gpu.py and the wide-sigma argmin test here."""
+tests/test_configs_gpu.py, tests/test_ctl_gpu.py and the wide-sigma argmin test here.
+
+The look-ahead tests here run at Ts = 0.02, R = diag(5e-3, 1) and the lanes per rollout the
+launch picks for their sizes (LPM 4 except where a test says otherwise); the table of kernel
+variants — integrator x LPM x staged / unstaged x lane group, with other time steps, weighted
+costs, the feasibility mask and an input_acc bank — is tests/test_lookahead_matrix_gpu.py.  The
+raceline test below takes its LPM 2 / 1 and weighted-cost rows from that table."""
 import os
 
 import numpy as np
@@ -1360,13 +1366,27 @@ def test_setupnlp_within_1pct_of_local_optimum(nat):
         assert fval <= 1.01 * g["fstar"][i], (int(g["tick"][i]), fval, g["fstar"][i])
 
 
-@pytest.mark.parametrize("track_name,start", [("ETHZ", "projected"), ("ETHZ", "lap_end"), ("ETHZMobil", "projected")])
-def test_lookahead_raceline_per_model_xref(nat, track_name, start):
+_DIAG_QP = (np.diag([2.0, 0.5]), np.diag([3.0, 0.25]))       # the LPM-4 position split
+
+
+@pytest.mark.parametrize("track_name,start,lpm,QP", [
+    pytest.param("ETHZ", "projected", None, None, id="ETHZ-projected"),
+    pytest.param("ETHZ", "lap_end", None, None, id="ETHZ-lap_end"),
+    pytest.param("ETHZMobil", "projected", None, None, id="ETHZMobil-projected"),
+    pytest.param("ETHZ", "projected", "2", None, id="ETHZ-projected-lpm2"),
+    pytest.param("ETHZ", "projected", "1", None, id="ETHZ-projected-lpm1"),
+    pytest.param("ETHZ", "projected", None, _DIAG_QP, id="ETHZ-projected-weighted"),
+    pytest.param("ETHZ", "projected", "2", _DIAG_QP, id="ETHZ-projected-lpm2-weighted"),
+    pytest.param("ETHZ", "projected", "1", _DIAG_QP, id="ETHZ-projected-lpm1-weighted")])
+def test_lookahead_raceline_per_model_xref(nat, monkeypatch, track_name, start, lpm, QP):
     """xref_mode RACELINE: every model's look-ahead tracks its own
     ConstantSpeed reference with mu_n = (Df_n + Dr_n) / (9.81 m), evaluated on the device
     from the raceline splines — against the oracle's ConstantSpeed loop (planner.py:34-65,
     pinned by tests/golden/planner.npz) per model.  Wide bank: mu_n below, inside and above
-    the profile range; 'lap_end' starts 3 cm before the lap length (the mod-L wrap)."""
+    the profile range; 'lap_end' starts 3 cm before the lap length (the mod-L wrap).  lpm: the
+    lanes per rollout forced with LLAMPC_LPM (None: the launch's own choice, 4 at this size),
+    asserted through llampc_plan_variant; QP: diagonal Q and terminal P instead of rt.py's."""
+    from llampc import _native
     from llampc.mpc import ModelBank, generate_bank, plan
     from llampc.mpc.planner import raceline_start
     from llampc.tracks import ETHZ, ETHZMobil
@@ -1392,6 +1412,13 @@ def test_lookahead_raceline_per_model_xref(nat, track_name, start):
     assert mu.min() < ref.mus[0] and mu.max() > ref.mus[-1]
     traj = O.rollout_rk4(shared(), tuple(p), x0, U, TS)
     Q, R, P = np.eye(2), np.diag([5e-3, 1]), np.zeros((2, 2))
+    if QP is not None:
+        Q, P = QP
+    if lpm is None:
+        monkeypatch.delenv("LLAMPC_LPM", raising=False)
+    else:
+        monkeypatch.setenv("LLAMPC_LPM", lpm)
+    assert _native.plan_variant(N, C, H)["lpm"] == int(lpm or 4)
     cref = np.empty((N, C))
     for n in range(N):
         xr, _ = O.constant_speed_from(s0, x0[:2], v0, ref, H, TS, scale, mu[n])
@@ -1399,9 +1426,12 @@ def test_lookahead_raceline_per_model_xref(nat, track_name, start):
     with ModelBank(p, device=0) as b:
         b.set_raceline(tr)
         res = plan(b, x0, uprev, x0, None, U, uprev=uprev, Ts=TS, do_lookback=False,
+                   cost=None if QP is None else _native.cost_struct(Q=Q, R=R, P=P),
                    return_costs=True, raceline_start=(s0, v0, scale))
     close(res.costs, cref, RTOL_ROLL)
     assert res.global_best[0] * C + res.global_best[1] == int(np.argmin(np.where(np.isnan(cref), np.inf, cref).ravel()))
+    print(f"MATRIX G (rk4, {int(lpm or 4)}, raceline) {track_name} {start} weighted={QP is not None}: "
+          f"err {np.max(np.abs(res.costs - cref) / np.abs(cref)):.2e}")
 
 
 @pytest.mark.parametrize("C,gap", [(64, 1e-9), (64, 1e-12), (8, 1e-7)])

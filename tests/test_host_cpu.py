@@ -42,6 +42,66 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_native.CtlOut) == _native.PLAN_OUT_BYTES + 56 + 16 * _native.HMAX
 
 
+def test_plan_variant_dispatch(monkeypatch):
+    """llampc_plan_variant (host only) reports what launch_plan picks for the given-xref layout:
+    lanes per rollout 4 -> 2 -> 1 as n * G * share passes 16384 and 32768 (G = 1: at the exact
+    lane count; G = 64: at the last / first n on either side), share = 2 halving both, RK6
+    always 1, the LLAMPC_LPM override honoured only while v * G <= 256, G / cpl from C, and the
+    LDS staging while 192 + 16 (H + 1) + 64 C H <= 128 KiB."""
+    from llampc import _native as nat
+    monkeypatch.delenv("LLAMPC_LPM", raising=False)
+    lpm = lambda n, C_, integ="rk4", share=1: nat.plan_variant(n, C_, 12, integ, share)["lpm"]
+    for integ in ("rk4", "euler_nlp"):
+        assert [lpm(n, 1, integ) for n in (16384, 16385, 32768, 32769)] == [4, 2, 2, 1]
+        assert [lpm(n, 64, integ) for n in (256, 257, 512, 513)] == [4, 2, 2, 1]
+        assert [lpm(n, 1, integ, 2) for n in (8192, 8193, 16384, 16385)] == [4, 2, 2, 1]
+        assert [lpm(n, 64, integ, 2) for n in (128, 129, 256, 257)] == [4, 2, 2, 1]
+    assert [lpm(n, C_, "rk6") for n, C_ in ((1, 1), (97, 3), (97, 64), (10 ** 5, 1))] == [1, 1, 1, 1]
+    # a model wider than a quarter / half of the block cannot take 4 / 2 lanes per rollout
+    assert [lpm(3, C_) for C_ in (64, 65, 128, 129, 256, 1000)] == [4, 2, 2, 1, 1, 1]
+    for C_, G, cpl in ((1, 1, 1), (2, 2, 1), (3, 4, 1), (64, 64, 1), (65, 128, 1), (130, 256, 1), (257, 256, 2),
+                       (1000, 256, 4)):
+        v = nat.plan_variant(97, C_, 12)
+        assert (v["G"], v["cpl"]) == (G, cpl), (C_, v)
+    # the override: taken while v * G <= 256 (whatever the lane count), ignored beyond
+    for env, cases in (("4", ((10 ** 6, 64, 4), (97, 65, 2), (97, 130, 1))),
+                       ("2", ((10 ** 6, 128, 2), (97, 3, 2), (97, 130, 1))),
+                       ("1", ((97, 3, 1), (97, 130, 1))),
+                       ("3", ((97, 3, 4), (10 ** 6, 3, 1)))):
+        monkeypatch.setenv("LLAMPC_LPM", env)
+        for n, C_, want in cases:
+            assert lpm(n, C_) == want, (env, n, C_)
+        assert lpm(97, 3, "rk6") == 1
+    monkeypatch.delenv("LLAMPC_LPM")
+    # staging: the largest H whose records fit, and the next, per C
+    for C_ in (1, 2, 3, 8, 64, 130, 256):
+        fits = lambda H: 192 + 16 * (H + 1) + 64 * C_ * H <= 128 * 1024
+        H = max(h for h in range(1, 2000) if fits(h))
+        assert nat.plan_variant(97, C_, H)["stage"] and not nat.plan_variant(97, C_, H + 1)["stage"], (C_, H)
+    assert [nat.plan_variant(97, C_, H)["stage"] for C_, H in ((64, 31), (64, 32), (130, 15), (130, 16), (3, 12),
+                                                               (64, 40), (130, 20), (2, 64))] == \
+        [True, False, True, False, True, False, False, True]
+    for bad in ((0, 3, 12, 0), (97, 0, 12, 0), (97, 3, 0, 0), (97, 3, 12, 3)):
+        with pytest.raises(nat.NativeError):
+            nat.plan_variant(*bad)
+
+
+def test_candidates_feasible_pwm_rate_bound():
+    """The oracle's optional pwm rate bound: None (the default) leaves the mask as before; a
+    value bounds |pwm_k - pwm_{k-1}| (step 0 against uprev) with the same relative tolerance."""
+    Ts, up = 0.02, np.array([0.3, 0.0])
+    U = np.zeros((4, 5, 2))
+    U[:, :, 0] = 0.3
+    U[1, 2:, 0] = 0.3 + 8.0 * Ts                   # a step of exactly the bound
+    U[2, 2:, 0] = 0.3 + 8.0 * Ts * (1 + 1e-6)      # just beyond it
+    U[3, :, 0] = 0.5                               # step 0 against uprev
+    args = (U, up, [-0.1, -0.35], [1.0, 0.35], 5.0, Ts)
+    assert list(O.candidates_feasible(*args)) == [True] * 4
+    assert list(O.candidates_feasible(*args, rate_max_pwm=None)) == [True] * 4
+    assert list(O.candidates_feasible(*args, rate_max_pwm=8.0)) == [True, True, False, False]
+    assert list(O.candidates_feasible(*args, rate_max_pwm=-1.0)) == [True] * 4
+
+
 def test_no_device_fails_loudly():
     """Without a GPU the product raises instead of falling back to the CPU."""
     from llampc import _native
