@@ -1,0 +1,224 @@
+// capi_host.hpp — the C ABI's host arithmetic (capi*.hip): sequence numbers, poll bounds, the
+// input pack, the window unroll and the launch-argument fields that come from the bank.  Pure:
+// no HIP runtime call, so tests/native/capi_host.cpp runs all of it on a machine with no GPU.
+#pragma once
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "ctl.hpp"
+#include "kernels.hpp"
+#include "nlp.hpp"
+
+namespace llampc {
+namespace {
+
+inline VehK make_veh(const llampc_vehicle& v) {
+  VehK k;
+  k.lf = v.lf;
+  k.lr = v.lr;
+  k.mass = v.mass;
+  k.inv_mass = 1 / v.mass;  // the reference's `1/self.mass` scalar (dynamic.py:111-112)
+  k.inv_Iz = 1 / v.Iz;      // `1/self.Iz` (dynamic.py:113)
+  k.Cm1 = v.Cm1;
+  k.Cm2 = v.Cm2;
+  k.Cr0 = v.Cr0;
+  k.Cr2 = v.Cr2;
+  k.input_acc = v.input_acc;
+  k.approx = v.approx;
+  return k;
+}
+
+// The constants an integrator sees: the NLP transcription (Dynamic.casadi + Euler,
+// dynamic.py:214-218, nmpc.py:58-60) always uses the pwm motor model and the Pacejka tires,
+// so input_acc / approx apply to the batch (RK4 / RK6) forms only.
+inline VehK integrator_veh(VehK k, int32_t integrator) {
+  if (integrator == LLAMPC_EULER_NLP) {
+    k.input_acc = 0;
+    k.approx = 0;
+  }
+  return k;
+}
+
+inline CostK make_cost(const llampc_cost& c, double Ts) {
+  CostK k;
+  for (int i = 0; i < 4; ++i) {
+    k.Q[i] = c.Q[i];
+    k.R[i] = c.R[i];
+    k.P[i] = c.P[i];
+  }
+  for (int i = 0; i < 2; ++i) {
+    k.umin[i] = c.umin[i];
+    k.umax[i] = c.umax[i];
+    // nmpc.py:104-105, tested with a relative tolerance of 1e-9: a sequence rate-clipped to the
+    // bound (u_k = u_{k-1} + rate Ts, the candidate samplers) can exceed it by one rounding
+    // of u_k - u_{k-1}; IPOPT itself accepts violations up to constr_viol_tol (1e-4)
+    k.dmax[i] = c.rate_max[i] < 0 ? -1.0 : c.rate_max[i] * Ts * (1.0 + 1e-9);
+  }
+  k.enforce = c.enforce_bounds;
+  k.pad = 0;
+  return k;
+}
+
+// The polled completion's wait bound in s_memrealtime ticks (100 MHz): a 2 s floor plus
+// 40 ns per look-ahead rollout step of the launch (a rate floor of 2.5e7 steps/s, ~10^3
+// below the fast path's, so the general-path re-runs, the raceline walker and launches
+// sharing the chip all fit).  A valid long tick (n = 1e7, C = 64, H = 40: ~4 s) therefore
+// never reads as a timeout; only a poll that could never finish does.
+// LLAMPC_POLL_BOUND_S overrides the floor and LLAMPC_POLL_STEP_NS the per-step term (tests).
+inline uint64_t poll_bound_ticks(int64_t n, int32_t C, int32_t H) {
+  double floor_s = 2.0, step_ns = 40.0;
+  if (const char* e = getenv("LLAMPC_POLL_BOUND_S")) floor_s = std::max(0.0, atof(e));
+  if (const char* e = getenv("LLAMPC_POLL_STEP_NS")) step_ns = std::max(0.0, atof(e));
+  const double steps = (double)n * (double)C * (double)H;    // <= 2^57 (check_plan_in)
+  const double ticks = 1e8 * floor_s + 0.1 * step_ns * steps;
+  return ticks >= 1.8e19 ? ~0ull : (uint64_t)ticks;
+}
+
+// A bound of s_memrealtime ticks in the kernels' units of 2^16 ticks: rounded up, at least one,
+// at most `max` (the width of the launch field that takes it).  The sum wraps in 64 bits: the
+// last 0xFFFF tick values, poll_bound_ticks' ~0ull among them, give one unit.
+inline uint64_t poll_units(uint64_t ticks, uint64_t max) {
+  return std::min(std::max<uint64_t>((ticks + 0xFFFF) >> 16, 1), max);
+}
+
+// Next tick number of a tag sequence: never 0 (the zeroed buffers' tag), and the parity
+// alternates across the 32-bit wrap (0xFFFFFFFF -> 2), so consecutive ticks of a peer
+// mailbox always use different slots (seq & 1).  Callers commit it only after the launch
+// that uses it was enqueued: a failed launch must not leave this rank a tick ahead.
+inline uint32_t next_seq(uint32_t s) { return s == 0xFFFFFFFFu ? 2u : s + 1u; }
+
+// Doubles of the packed inputs: x_prev[6] u_prev[2] x_now[6] uprev[2] xref[2][H+1] U[C][H][2].
+inline size_t pack_len(const llampc_plan_in* in) {
+  const int64_t H = in->do_lookahead ? in->H : 0, C = in->do_lookahead ? in->C : 0;
+  return 16 + 2 * (H + 1) + 2 * C * H;
+}
+
+inline void pack_into(const llampc_plan_in* in, double* h) {
+  const int64_t H = in->do_lookahead ? in->H : 0, C = in->do_lookahead ? in->C : 0;
+  std::memset(h, 0, 16 * sizeof(double));
+  if (in->x_prev) std::memcpy(h + 0, in->x_prev, 6 * sizeof(double));
+  if (in->u_prev) std::memcpy(h + 6, in->u_prev, 2 * sizeof(double));
+  if (in->x_now) std::memcpy(h + 8, in->x_now, 6 * sizeof(double));
+  if (in->uprev) std::memcpy(h + 14, in->uprev, 2 * sizeof(double));
+  if (in->do_lookahead) {
+    if (in->xref_mode == LLAMPC_XREF_RACELINE) {       // {s0, v0, scale, 0} (<= 2(H+1) slots)
+      std::memset(h + 16, 0, 2 * (H + 1) * sizeof(double));
+      std::memcpy(h + 16, in->xref, 3 * sizeof(double));
+    } else {
+      std::memcpy(h + 16, in->xref, 2 * (H + 1) * sizeof(double));
+    }
+    std::memcpy(h + 16 + 2 * (H + 1), in->U, 2 * C * H * sizeof(double));
+  }
+}
+
+// The look-back ring [W][n] (slot-major; `slot` is the next row to write, `count` rows filled)
+// in the rt.py layout [n][W]: newest in column W-1, unfilled (oldest) columns zero.
+inline void window_unroll(const double* raw, int64_t n, int32_t W, int32_t count, int32_t slot, double* ring) {
+  for (int64_t i = 0; i < n; ++i) {
+    for (int c = 0; c < W; ++c) {
+      const int age = W - 1 - c;                   // 0 = newest
+      double v = 0.0;
+      if (age < count) {
+        const int s = ((slot - 1 - age) % W + W) % W;
+        v = raw[(size_t)s * n + i];
+      }
+      ring[(size_t)i * W + c] = v;
+    }
+  }
+}
+
+// What the launches take from a bank: its device buffers by address and its sizes
+// (bank_view builds one per tick, on the stack).
+struct BankView {
+  const double* params;                  // [6][n]
+  int64_t n, goff;
+  VehK veh;
+  double* ring;                          // [W][n]
+  int32_t W, slot;
+  double* wmean;                         // [n]
+  double* am_val;  int64_t* am_idx;
+  double* tk_val;  int64_t* tk_idx;
+  const double* rl;                      // raceline table: knots | xy | speed | mus (or null)
+  int32_t rl_n, rl_M;
+  double rl_hmin, rl_vmax;
+};
+
+// The raceline table's sections (llampc_bank_set_raceline's layout).  wcap = 0: the plan launch
+// sets it from the LDS it leaves; the controller's launch holds the whole lap.
+inline RacelineK raceline_view(const BankView& b) {
+  const size_t m = (size_t)b.rl_n - 1;
+  RacelineK r;
+  r.knots = b.rl;
+  r.xy = b.rl + b.rl_n;
+  r.speed = r.xy + 8 * m;
+  r.mus = r.speed + 4 * m * b.rl_M;
+  r.n = b.rl_n;
+  r.M = b.rl_M;
+  r.wcap = 0;
+  r.hmin = b.rl_hmin;
+  r.vmax = b.rl_vmax;
+  return r;
+}
+
+// The bank's part of a tick's launch arguments, the same for a plan tick and a controller tick.
+inline void bank_lookback(const BankView& b, LookbackLaunch& l) {
+  l.params = b.params;
+  l.n = b.n;
+  l.goff = b.goff;
+  l.veh = b.veh;
+  l.ring = b.ring;
+  l.W = b.W;
+  l.slot = b.slot;
+  l.wm_buf = b.wmean;
+  l.am_val = b.am_val;
+  l.am_idx = b.am_idx;
+  l.tk_val = b.tk_val;
+  l.tk_idx = b.tk_idx;
+}
+
+inline void bank_lookahead(const BankView& b, int32_t integrator, LookaheadLaunch& l) {
+  l.params = b.params;
+  l.n = b.n;
+  l.goff = b.goff;
+  l.veh = integrator_veh(b.veh, integrator);
+  l.integrator = integrator;
+}
+
+inline void bank_final(const BankView& b, FinalLaunch& f) {
+  f.n = b.n;
+  f.goff = b.goff;
+  f.params = b.params;
+  f.am_val = b.am_val;
+  f.am_idx = b.am_idx;
+  f.tk_val = b.tk_val;
+  f.tk_idx = b.tk_idx;
+}
+
+// Spins until *tag == want (acquire): 0.  A tag that `stop` accepts ends the spin with
+// kSpinStopped.  After `bound`, on_timeout() runs once (it synchronises the stream, so a HIP
+// error is the one reported: its non-zero return, an LLAMPC_E_* code, is passed on as it is); a
+// tag still missing then gives kSpinTimeout.  Both outcomes are > 0, which no LLAMPC_* code is.
+constexpr int kSpinStopped = 1, kSpinTimeout = 2;
+template <class OnTimeout, class Stop = bool (*)(uint64_t)>
+inline int spin_for_tag(const uint64_t* tag, uint64_t want, OnTimeout on_timeout,
+                        Stop stop = [](uint64_t) { return false; },
+                        std::chrono::nanoseconds bound = std::chrono::seconds(10)) {
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t spins = 0;
+  uint64_t v;
+  while ((v = __atomic_load_n(tag, __ATOMIC_ACQUIRE)) != want) {
+    __builtin_ia32_pause();
+    if (stop(v)) return kSpinStopped;
+    if ((++spins & 0xFFF) == 0 && std::chrono::steady_clock::now() - t0 > bound) {
+      if (int rc = on_timeout()) return rc;
+      return __atomic_load_n(tag, __ATOMIC_ACQUIRE) == want ? 0 : kSpinTimeout;
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+}  // namespace llampc

@@ -1,0 +1,173 @@
+// capi_nlp.hip — the setupNLP.solve drop-in's host side (llampc_nlp_*, include/llampc.h;
+// nlp.hip): CEM iterations enqueued back to back on the bank's stream, the Euler trajectory of
+// the best sequence, the result through pinned host memory.
+#include "capi_common.hpp"
+
+using namespace llampc;
+
+static_assert(sizeof(llampc_nlp_cfg) == 16 + 8 + 16 + 8 + 8 + sizeof(llampc_cost) + 32, "llampc_nlp_cfg layout");
+
+struct __attribute__((visibility("hidden"))) llampc_nlp {
+  llampc_bank* b = nullptr;
+  llampc_nlp_cfg cfg{};
+  DevBuf<NlpState> d_st;                 // the best so far across a solve's launches (device);
+                                         // the inputs travel as kernel arguments (NlpInline)
+  DevBuf<double> d_cost;                 // the sample blocks' sorted lists as tagged words
+                                         // [2][3][samples], then the rounds' rate-clipped
+                                         // sequences [2][samples][H][2] (NlpLaunch.list_tag, cand;
+                                         // by round parity)
+  DevBuf<uint64_t> d_ms_tag;             // [2][4 HMAX]: a round's mean / std (NlpLaunch.ms_tag)
+  bool per_round = false;                // one launch per round (LLAMPC_NLP_ROUND_LAUNCHES=1: A/B)
+  bool ltraj = false;                    // the last round keeps its states in LDS (NlpLaunch.ltraj;
+                                         // LLAMPC_NLP_RERUN_TRAJ=1 at create: always re-run, tests)
+  MappedRecord<NlpResult> host;          // the last round writes the result, then the solve's number
+  uint64_t calls = 0;
+  std::mutex mu;
+};
+
+extern "C" {
+
+int llampc_nlp_destroy(llampc_nlp* p) {
+  if (!p) return LLAMPC_OK;
+  DeviceGuard g(p->b->device);
+  if (p->b->stream) (void)hipStreamSynchronize(p->b->stream);
+  delete p;
+  return LLAMPC_OK;
+}
+
+int llampc_nlp_create(llampc_bank* b, const llampc_nlp_cfg* cfg, llampc_nlp** out) {
+  if (!out) return fail(LLAMPC_E_ARG, "out is NULL");
+  *out = nullptr;
+  if (!b || !cfg) return fail(LLAMPC_E_ARG, "NULL argument");
+  const llampc_nlp_cfg& k = *cfg;
+  if (b->n != 1) return fail(LLAMPC_E_ARG, "the NLP solver's bank holds one model (n=%lld)", (long long)b->n);
+  if (k.H < 1 || k.H > LLAMPC_HMAX) return fail(LLAMPC_E_ARG, "H=%d outside [1, %d]", k.H, LLAMPC_HMAX);
+  if (k.samples < 64 || k.samples > 4096 || (k.samples & (k.samples - 1)))
+    return fail(LLAMPC_E_ARG, "samples=%d: a power of two in [64, 4096]", k.samples);
+  if (k.elite < 1 || k.elite > 64 || k.elite > k.samples || k.iters < 1 || k.iters > kNlpMaxIters)
+    return fail(LLAMPC_E_ARG, "elite=%d (1..64, <= samples) iters=%d (1..%d)", k.elite, k.iters, kNlpMaxIters);
+  if (!(k.Ts > 0) || !std::isfinite(k.Ts)) return fail(LLAMPC_E_ARG, "Ts must be finite > 0");
+  if (nlp_lds_bytes(k.H, k.samples, k.elite) > 160 * 1024) return fail(LLAMPC_E_ARG, "H x elite too large for LDS");
+  DeviceGuard g(b->device);
+  Building<llampc_nlp> p(new llampc_nlp(), llampc_nlp_destroy);
+  p->b = b;
+  p->cfg = k;
+  const size_t H = (size_t)k.H;
+  int rc;
+  // the lists: 3 words per entry, samples / 64 x len <= samples entries; both by round parity.
+  // Tagged words start at tag 0, which no solve uses (nlp_seq of a solve number >= 1)
+  if ((rc = p->d_st.zalloc(1)) || (rc = p->d_cost.zalloc((size_t)k.samples * (6 + 4 * H))) ||
+      (rc = p->d_ms_tag.zalloc(8 * (size_t)LLAMPC_HMAX)) || (rc = p->host.alloc("NLP result")))
+    return rc;
+  {
+    // every round in one launch needs all samples / 64 blocks resident together (each waits for
+    // the others' rounds; one block per CU by its LDS request): not on a device, or a partition
+    // of one, with fewer CUs than blocks — then one launch per round
+    const char* e = std::getenv("LLAMPC_NLP_ROUND_LAUNCHES");
+    const bool resident = k.samples / 64 <= b->cus;
+    p->per_round = !nlp_persistent(k.samples) || !resident || (e && e[0] == '1');
+    const char* rt = std::getenv("LLAMPC_NLP_RERUN_TRAJ");
+    p->ltraj = nlp_ltraj_fits(k.H, k.samples, k.elite) && !(rt && rt[0] == '1');
+  }
+  if (hipDeviceSynchronize() != hipSuccess)
+    return fail(LLAMPC_E_HIP, "NLP solver upload failed");
+  *out = p.release();
+  return LLAMPC_OK;
+}
+
+int llampc_nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const double* uprev, const double* base,
+                     int32_t has_hold, double* umpc, double* fval, double* xmpc) {
+  if (!p || !x0 || !xref || !uprev || !umpc) return fail(LLAMPC_E_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lp(p->mu);
+  llampc_bank* b = p->b;
+  std::lock_guard<std::mutex> lk(b->mu);
+  bank_disarm(b);
+  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
+  DeviceGuard g(b->device);
+  const llampc_nlp_cfg& k = p->cfg;
+  const int H = k.H;
+  hipStream_t s = b->stream;
+  // the launch's inputs (NlpInline): x0, xref, the first mean (base or uprev held); the first
+  // std is sigma0, the best so far starts at +inf (the kernel's round 0)
+  NlpInline pk;
+  std::memcpy(pk.v, x0, 6 * sizeof(double));
+  std::memcpy(pk.v + 6, xref, 2 * (size_t)(H + 1) * sizeof(double));
+  double* m0 = pk.v + 6 + 2 * (H + 1);
+  for (int i = 0; i < H; ++i)
+    for (int j = 0; j < 2; ++j) m0[2 * i + j] = base ? base[2 * i + j] : uprev[j];
+  NlpLaunch a{};
+  a.la.params = b->d_params.get();
+  a.la.n = 1;
+  a.la.veh = integrator_veh(b->veh, LLAMPC_EULER_NLP);
+  a.la.C = 64;
+  a.la.H = H;
+  a.la.integrator = LLAMPC_EULER_NLP;
+  a.la.Ts = k.Ts;
+  a.la.cost = make_cost(k.cost, k.Ts);
+  a.st = p->d_st.get();
+  a.list_tag = reinterpret_cast<uint64_t*>(p->d_cost.get());
+  a.cand = p->d_cost.get() + 6 * (size_t)k.samples;
+  a.res = p->host.rec.dev();
+  a.host_tag = p->host.tag.dev();
+  a.host_seq = p->calls + 1;
+  a.ms_tag = p->d_ms_tag.get();
+  a.ltraj = p->ltraj;
+  a.seed = k.seed;
+  a.call = p->calls;
+  a.up0 = uprev[0];
+  a.up1 = uprev[1];
+  a.umin0 = k.cost.umin[0];
+  a.umin1 = k.cost.umin[1];
+  a.umax0 = k.cost.umax[0];
+  a.umax1 = k.cost.umax[1];
+  a.rlo0 = k.rate_lo[0];
+  a.rlo1 = k.rate_lo[1];
+  a.rhi0 = k.rate_hi[0];
+  a.rhi1 = k.rate_hi[1];
+  a.std_floor = k.std_floor;
+  a.sig0 = k.sigma0[0];
+  a.sig1 = k.sigma0[1];
+  a.H = H;
+  a.samples = k.samples;
+  a.elite = k.elite;
+  a.has_hold = has_hold;
+  a.iters = k.iters;                    // the last round's completion writes xmpc (nmpc.py:58-60)
+  if (p->per_round) {
+    a.rounds = 1;
+    for (int it = 0; it < k.iters; ++it) {
+      a.it = it;
+      TimedLaunch tl(b, 0, s);           // llampc_bank_timing on the solver's bank: per round
+      HIP_TRY(launch_nlp(a, pk, s));
+    }
+  } else {                              // every round in one launch (nlp.hpp nlp_persistent)
+    a.it = 0;
+    a.rounds = k.iters;
+    TimedLaunch tl(b, 0, s);             // llampc_bank_timing on the solver's bank: per solve
+    HIP_TRY(launch_nlp(a, pk, s));
+  }
+  // the last round's completion writes the result into pinned memory and then the tag
+  const uint64_t want = p->calls + 1;
+  const int rc = spin_for_tag(p->host.tag.get(), want, [&]() -> int {
+    HIP_TRY(hipStreamSynchronize(s));
+    return LLAMPC_OK;
+  });
+  if (rc == kSpinTimeout) {
+    // the launch has ended (its blocks give up a round wait after kNlpRoundWait): the next
+    // solve must not meet this one's state — a new call number, so none of this solve's
+    // tagged words (lists, mean / std) matches a later round's tag
+    p->calls++;
+    return fail(LLAMPC_E_DEVICE, "NLP solve %llu: completion tag never arrived", (unsigned long long)want);
+  }
+  if (rc) return rc;
+  p->calls++;
+  b->launches += p->per_round ? k.iters : 1;
+  const NlpResult* r = const_cast<const NlpResult*>(p->host.rec.get());
+  for (int i = 0; i < H; ++i)
+    for (int j = 0; j < 2; ++j) umpc[2 * i + j] = r->best_u[i][j];
+  if (fval) *fval = r->best_j;
+  if (xmpc) std::memcpy(xmpc, &r->traj[0][0], 6 * (size_t)(H + 1) * sizeof(double));
+  if (r->best_it < 0) return fail(LLAMPC_E_DEVICE, "no finite objective in %d rounds of %d samples", k.iters, k.samples);
+  return LLAMPC_OK;
+}
+
+}  // extern "C"
