@@ -21,8 +21,11 @@
 // and never waits on a look-ahead block before it publishes (the selection comes before its
 // own poll).  The completion waits only for look-ahead blocks, which then never wait again.
 // Every wait has a bound (status LLAMPC_STATUS_POLL_TIMEOUT, never expected).
-#include "plan_dev.hpp"
 #include "ctl.hpp"
+#include "dev_wave.hpp"
+#include "final_dev.hpp"
+#include "lookback_dev.hpp"
+#include "rollout_dev.hpp"
 
 namespace llampc {
 
@@ -328,7 +331,7 @@ __device__ __forceinline__ void ctl_spec_lists(const CtlLaunch& c, int blk, doub
   ctl_spec_merge<PX>(c, smem);
 }
 
-// The deferred tracking cost (rollout<DEFER>): the split rollout's epilogue with the reference
+// The deferred tracking cost (rollout with kRDefer): the split rollout's epilogue with the reference
 // known — the same terms in the same order, so J equals the undeferred rollout's bitwise.
 __device__ __forceinline__ double defer_cost(const double* dpos, int dstride, const double* sx, int H, int pc,
                                              double Qd, double Pd, const DeferOut& d, bool sok, bool& bad) {
@@ -1239,6 +1242,8 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
   int64_t bc = kNoIndex;
   int nf = 0;
   constexpr bool kSplit = (LPM == 4);
+  constexpr unsigned kRF = kRUlds;                          // the re-run; the fast runs add to it
+  constexpr unsigned kRSplitQ = kSplit ? kRSplit : 0u;      // the quad's position split
   const bool diagQP = c.la.cost.Q[1] == 0.0 && c.la.cost.Q[2] == 0.0 && c.la.cost.P[1] == 0.0 && c.la.cost.P[2] == 0.0;
   if (live) {
     constexpr bool kScaled = scaled_yaw(LPM);
@@ -1260,17 +1265,14 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
       double J;
       if (c.s4) {                       // block-uniform: the staged input terms
         if (kSplit && diagQP)
-          J = rollout<0, false, LPM, 0, true, kSplit, true, false, true>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts,
-                                                                        up0, up1, K, fq, bad, nullptr, s4);
+          J = rollout<0, LPM, kRF | kRFast | kRS4 | kRSplitQ>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, bad,
+                                                              nullptr, s4);
         else
-          J = rollout<0, false, LPM, 0, true, false, true, false, true>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts,
-                                                                       up0, up1, K, fq, bad, nullptr, s4);
+          J = rollout<0, LPM, kRF | kRFast | kRS4>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, bad, nullptr, s4);
       } else if (kSplit && diagQP) {
-        J = rollout<0, false, LPM, 0, true, kSplit, true>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K,
-                                                         fq, bad);
+        J = rollout<0, LPM, kRF | kRFast | kRSplitQ>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, bad);
       } else {
-        J = rollout<0, false, LPM, 0, true, false, true>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K,
-                                                        fq, bad);
+        J = rollout<0, LPM, kRF | kRFast>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, bad);
       }
       if (LPM == 2) {
         const int bi = bad;
@@ -1284,8 +1286,7 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
       if (__builtin_expect(__any(bad), 0)) {
         bool unused = false;
         if (bad)
-          J = rollout<0, false, LPM, 0, false, false, true>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K,
-                                                           fq, unused);
+          J = rollout<0, LPM, kRF>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, unused);
       }
       if (sub == 0) nf += !isfinite(J);
       if (less_nan_last(J, cc, bv, bc)) {
@@ -1342,7 +1343,7 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
 // A spec block: model spec_tag[j] x the C candidates from the doorbell on (ctl.hpp
 // CtlLaunch.n_spec).  Before the doorbell: the candidates (the look-ahead blocks' generator, so
 // the same sequences), the rate clip, the staged terms, the model.  Then the rollouts with the
-// tracking cost deferred (rollout<DEFER>), the reference from the first look-ahead block's walk
+// tracking cost deferred (rollout with kRDefer), the reference from the first look-ahead block's walk
 // (xref_tag), defer_cost, and the block's best candidate as ctl_lookahead publishes a slot.
 // LPM 4 with diagonal Q / P only (the host enables spec blocks for that layout).
 template <int LPM>
@@ -1431,9 +1432,8 @@ __device__ __forceinline__ void ctl_spec(const CtlLaunch& c, int j, unsigned cha
     bool bad = false;
     DeferOut d{};
     (void)cpl;
-    (void)rollout<0, false, LPM, 0, true, true, true, false, true, true>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts,
-                                                                         up0, up1, K, fq, bad, nullptr, s4, dp, ds,
-                                                                         &d);
+    (void)rollout<0, LPM, kRUlds | kRFast | kRS4 | kRSplit | kRDefer>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K,
+                                                                      fq, bad, nullptr, s4, dp, ds, &d);
     CTL_STAMP(blockIdx.x, 20);
     // the reference: the walker's tagged halves (its walk ended long before these rollouts)
     {
@@ -1461,8 +1461,7 @@ __device__ __forceinline__ void ctl_spec(const CtlLaunch& c, int j, unsigned cha
     if (__builtin_expect(__any(bad), 0)) {
       bool unused = false;
       if (bad)
-        J = rollout<0, false, LPM, 0, false, false, true>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq,
-                                                         unused);
+        J = rollout<0, LPM, kRUlds>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, unused);
     }
     double bv = __builtin_nan("");
     int64_t bc = kNoIndex;

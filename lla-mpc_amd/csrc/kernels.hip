@@ -15,9 +15,18 @@
 //                      model.py:18-40, rk6.py).
 //
 // This translation unit: the plan-launch dispatcher (launch_plan) and the non-plan kernels.
-// The device code of the plan launch is plan_dev.hpp; its instantiations live in plan_*.hip
+// The plan kernels are in plan_dev.hpp (their device code in the *_dev.hpp role headers), their
+// instantiations in plan_*.hip
 // (one TU per variant group, so the library builds in parallel), the controller tick in ctl.hip.
-#include "plan_dev.hpp"
+#include <stdlib.h>
+
+#include <algorithm>
+
+#include "dev_wave.hpp"
+#include "final_dev.hpp"
+#include "lookback_dev.hpp"
+#include "peer_dev.hpp"
+#include "rollout_dev.hpp"
 
 namespace llampc {
 

@@ -162,6 +162,16 @@ extern template void launch_plan_inline_group<2>(const LookbackLaunch&, const Lo
                                                  int, int, size_t, hipStream_t, const InlinePack&);
 extern template void launch_plan_inline_group<1>(const LookbackLaunch&, const LookaheadLaunch&, const FinalLaunch&,
                                                  int, int, size_t, hipStream_t, const InlinePack&);
+// Lets a kernel ask for the CU's whole LDS (every launcher of a kernel with dynamic LDS).
+template <typename KERN>
+static void allow_lds(KERN k) {
+  static bool done = false;             // once per instantiation (idempotent if raced)
+  if (!done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(160 * 1024));
+    done = true;
+  }
+}
 hipError_t launch_merge(const llampc_plan_out* parts, int32_t G, int32_t nan_first,
                         llampc_plan_out* merged, hipStream_t s);
 // Peer exchange of the sharded tick (peer_exchange_kernel): mailbox g is [2][G][kRecWords]

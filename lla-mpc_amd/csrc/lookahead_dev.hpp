@@ -1,0 +1,507 @@
+// lookahead_dev.hpp — the plan launch's look-ahead block: the shared inputs staged in LDS
+// (or the per-model raceline reference walked), every (model, candidate) of the block rolled
+// out, the per-model argmin and the block's partial published (la_publish).  Included by
+// plan_dev.hpp only; the controller and the NLP solve have look-ahead bodies of their own.
+#pragma once
+#include "dev_stamps.hpp"
+#include "dev_wave.hpp"
+#include "raceline.hpp"
+#include "rollout_dev.hpp"
+
+namespace llampc {
+
+// ------------------------------------------------------------------------------------
+// Look-ahead body.  Lane layout inside a block: sub = lane % LPM (LPM = 2: the lane pair
+// of one rollout, front/rear chain), cl = lane / LPM; G candidate-lanes per model (power of two); a model's
+// candidates c = g + j*G, j < cpl, run sequentially in its G*LPM lanes.
+//   LDS from kScratchBytes: xref as [k][2]; U as [k][c][kStageW] (RK4: F0, F1, h/m sin,
+//   h/m cos, h lf/Iz cos, delta; else pwm, delta, sin, cos; then
+//   input-rate cost term, feasibility) when staged.
+// ------------------------------------------------------------------------------------
+// The block's partial of the look-ahead argmin over (model, candidate) in flattened order
+// (goff+n)*C + c — (v, key) per lane (kNoIndex: none) and the lanes' non-finite counts:
+// branch-free wave picks, one LDS exchange, thread 0 publishes (tagged words or plain).
+template <int NW = kWaves>
+__device__ __forceinline__ void la_publish(const LookaheadLaunch& a, int blk, const Scratch& sc, int par,
+                                           double v, int64_t key, int nf) {
+  // NW = 8 (the work-queue block) uses both halves of sv / si (par = 0 there) and sn[4..8)
+  static_assert(NW == kWaves || NW == 8, "4- or 8-wave blocks");
+  wave_pick_nl64(v, key);
+  const int nfw = wave_sum(nf);
+  double* sv = sc.sv + 4 * par;         // the buffer a span > 64 exchange did not use
+  int64_t* si = sc.si + 4 * par;
+  if ((threadIdx.x & 63) == 0) {
+    sv[threadIdx.x >> 6] = v;
+    si[threadIdx.x >> 6] = key;
+    sc.sn[threadIdx.x >> 6] = nfw;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int nfs = sc.sn[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+      const bool t = (int)(si[w] != kNoIndex) & (int)less_bf<0>(sv[w], si[w], v, key);
+      v = t ? sv[w] : v;
+      key = t ? si[w] : key;
+      nfs += sc.sn[w];
+    }
+    if (a.poll) {
+      uint64_t* r = a.blk_tag + 5 * (int64_t)blk;
+      const uint64_t vb = (uint64_t)__double_as_longlong(v), kb = (uint64_t)key;
+      st_wt(&r[0], tag_word(a.seq, (uint32_t)(vb >> 32)));
+      st_wt(&r[1], tag_word(a.seq, (uint32_t)vb));
+      st_wt(&r[2], tag_word(a.seq, (uint32_t)(kb >> 32)));
+      st_wt(&r[3], tag_word(a.seq, (uint32_t)kb));
+      st_wt(&r[4], tag_word(a.seq, (uint32_t)nfs));
+    } else {
+      st_wt(&a.pv[blk], v);
+      st_wt(&a.pidx[blk], key);
+      st_wt(&a.pnf[blk], nfs);
+    }
+  }
+}
+
+// WQ (the throughput regime, launch_plan): a persistent layout — the grid holds one look-ahead
+// block per CU and each wave takes units of 64 / G models (one model at G = 64) from the
+// bank's work counter, so the staging prologue runs once per CU instead of once per 4 models
+// and no CU waits for a new block between units (v29 stamps at C = 64: prologue 3.4 us and
+// reduction 2 us of each 45 us block).
+template <int INTEG, bool STAGE, int LPM, int XM, int WQ = 0>
+__device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int blk, int G, int cpl,
+                                                unsigned char* smem, const Scratch& sc) {
+  LA_STAMP(blk, 0);
+  constexpr int BT = wq_threads(WQ);   // threads of this block
+  double* sx = reinterpret_cast<double*>(smem + kScratchBytes);
+  double* su = sx + 2 * (a.H + 1);
+  const int H = a.H, C = a.C;
+  // this lane's model: its Pacejka row and the start state are loaded first, so they are in
+  // flight while the block stages the shared inputs (one HBM round trip, not two)
+  const int sub = threadIdx.x % LPM;
+  const int cl = threadIdx.x / LPM;
+  const int g = cl & (G - 1);
+  const int64_t n = (int64_t)blk * (kBlock / (G * LPM)) + cl / G;
+  const bool live = n < a.n;
+  // XM: threads [0, mpb) walk the raceline; the U staging below runs on the threads after
+  // them, so the two overlap (the walk is one lane's serial chain, latency-bound)
+  const int mpb = kBlock / (G * LPM);
+  const int soff = (XM && mpb < kBlock) ? mpb : 0;
+  Tire t{};
+  if (!WQ && live) t = load_tire(a.params, a.n, n);
+  double x0[6];
+#pragma unroll
+  for (int m = 0; m < 6; ++m) x0[m] = a.x0[m];
+  // XM = 1 (per-model raceline reference): knots [n] and the x/y spline rows [2][4][n-1]
+  // after the (optional) U staging; a.xref holds the shared start {s0, v0, scale}
+  double* rl_knots = su + (STAGE ? kStageW * C * H : 0);
+  double* rl_xy = rl_knots + a.rl.n + kKnotPad;
+  if (XM) {
+    const int nk = a.rl.n, nseg = a.rl.n - 1, nxy = 8 * nseg;
+    const double* gk = a.rl.knots;                          // knots | xy contiguous
+    const double* gmu = a.rl.mus;
+    double* rl_mus = rl_xy + nxy;                           // [M], then the speed window
+    // knots, the +inf pad (RaceRef::step), xy and mus in one batch (one memory round trip
+    // per thread at the ETHZ size)
+    copy_lds<4>(rl_knots, nk, [&](int e) { return gk[e]; });
+    copy_lds<24>(rl_xy, nxy + a.rl.M, [&](int e) {
+      const double* p = e < nxy ? gk + nk + e : gmu + (e - nxy);
+      return *p;
+    });
+    if ((int)threadIdx.x < kKnotPad) rl_knots[nk + threadIdx.x] = __builtin_inf();
+    // the window end: s0 plus the largest advance of H walker steps (one lap at most)
+    const double s0 = a.xref[0];
+    const double L = gk[nseg];
+    const double adv = window_adv(a.xref[1], a.xref[2], a.Ts, H, a.rl.vmax);
+    const bool bounded = adv < L && s0 >= 0.0 && s0 < L;
+    double te = s0 + adv;
+    if (te >= L) te -= L;
+    __syncthreads();
+    RL_STAMP(blk, 0);
+    // bisect-right of s0 and te on the knots (RaceRef::init's: the largest i in [1, n-2]
+    // with knots[i] <= s, else 0) as one parallel pass: with the knots ascending, exactly
+    // one segment i has (i == 0 or knots[i] <= s) and (i == n-2 or not knots[i+1] <= s),
+    // and it writes i.  XM leaves sx (the shared xref stage) unused: two ints there.
+    int* rl_sel = reinterpret_cast<int*>(sx);
+    for (int i = threadIdx.x; i < nseg; i += kBlock) {
+      const double ki = rl_knots[i], kn = rl_knots[i + 1];
+      const bool last = i == nseg - 1;
+      if ((i == 0 || ki <= s0) && (last || !(kn <= s0))) rl_sel[0] = i;
+      if ((i == 0 || ki <= te) && (last || !(kn <= te))) rl_sel[1] = i;
+    }
+    __syncthreads();
+    // the speed profiles' window (raceline.hpp SpeedWin): from the start segment to the
+    // window end; block-uniform
+    SpeedWin sw{nullptr, 0, 0};
+    const int seg0 = rl_sel[0];
+    {
+      const int lo = seg0, l2 = rl_sel[1];
+      const double need = bounded ? (double)(l2 >= lo ? l2 - lo : l2 + nseg - lo) + 2.0 : 1e300;
+#ifdef LLAMPC_STAMPS
+      if (blk == 0 && threadIdx.x == 0) {
+        g_rl_dbg[0] = need;
+        g_rl_dbg[1] = a.rl.wcap;
+        g_rl_dbg[2] = adv;
+        g_rl_dbg[3] = a.xref[0];
+        g_rl_dbg[4] = L;
+        g_rl_dbg[5] = a.rl.vmax;
+      }
+#endif
+      if (need <= (double)a.rl.wcap) {
+        double* wl = rl_mus + ((a.rl.M + 1) & ~1);          // 16-B aligned
+        sw.w = wl;
+        sw.seg0 = lo;
+        sw.W = (int)need;
+        const int W = sw.W, tot = a.rl.M * 4 * W;
+        const double* gsp = a.rl.speed;
+        // element e = row W + j; copy_lds asks for e = threadIdx.x + i kBlock in order, so
+        // (row, j) steps by kBlock without a division per element
+        int row = (int)threadIdx.x / W, j = (int)threadIdx.x - row * W;
+        const int drow = kBlock / W, dj = kBlock - drow * W, rows = a.rl.M * 4;
+        copy_lds<24>(wl, tot, [&](int) {          // (row, j) past the end: clamped rows
+          int sg = lo + j;
+          if (sg >= nseg) sg -= nseg;
+          const double v = gsp[(size_t)(row < rows ? row : rows - 1) * nseg + sg];
+          row += drow;
+          j += dj;
+          if (j >= W) {
+            j -= W;
+            ++row;
+          }
+          return v;
+        });
+        __syncthreads();
+      }
+    }
+    RL_STAMP(blk, 1);
+    // one thread per model of this block walks ConstantSpeed into xref_pm[m][H][2]
+    const int64_t m = (int64_t)blk * mpb + threadIdx.x;
+    if ((int)threadIdx.x < mpb && m < a.n) {
+      const double mu = (a.params[2 * a.n + m] + a.params[5 * a.n + m]) / (9.81 * a.veh.mass);
+      // the table descriptor in registers: the walk's global stores cannot alias it
+      const RacelineK rl = a.rl;
+      RaceRef rr;
+      rr.init(rl, rl_knots, rl_mus, mu, a.xref[0], a.xref[1], a.xref[2], a.Ts, seg0);
+      double2* out = reinterpret_cast<double2*>(a.xref_pm + m * 2 * H);
+      for (int k = 0; k < H; ++k) {
+        double xr, yr;
+        rr.step(rl, rl_knots, rl_xy, sw, xr, yr);
+        out[k] = make_double2(xr, yr);
+      }
+    }
+    RL_STAMP(blk, 2);
+    __threadfence_block();
+    RL_STAMP(blk, 3);
+  } else {
+    for (int e = threadIdx.x; e <= H; e += BT) {
+      sx[2 * e] = a.xref[e];
+      sx[2 * e + 1] = a.xref[(H + 1) + e];
+    }
+  }
+  // Shared xref: ONE FmK for the staging below and the rollouts (the staging uses its sincos
+  // constants, the same in the lean and precise sets) instead of materialising the ~50
+  // constants twice on the prologue's critical path; the raceline variant keeps two loads
+  // (holding them across its prologue spilled, round 1).
+  fm::FmK K0;
+  if constexpr (!XM) K0 = fm::FmK::load<kLeanLA && INTEG == 0>();
+  if (STAGE) {
+    // [k][c] -> (pwm, delta, sin delta, cos delta): the steering's sincos depends only on the
+    // shared candidates, so it is formed once per block here (same evaluation as
+    // make_input_fast: the fast core on its domain, the general function off it).  RK4
+    // stages the fused stages' input terms instead: (F0, F1, h/m sin d, h/m cos d,
+    // h lf/Iz cos d, delta) — dyn.hpp fused_in, with the shared constants of make_fused.
+    const fm::FmK K = [&] {
+      if constexpr (XM) return fm::FmK::load();
+      else return K0;
+    }();
+    const FusedK fq0 = make_fused(a.veh, make_stage<1>(a.veh, Tire{}, 0), a.Ts, scaled_yaw(LPM));
+    for (int e = (int)threadIdx.x - soff; e < C * H; e += BT - soff) {
+      if (e < 0) break;
+      const int c = e / H, k = e - c * H;
+      const double dl = a.U[2 * e + 1];
+      double sd, cd;
+      if (fm::sincos_fast_ok(dl)) fm::sincos_fast(dl, &sd, &cd, K);
+      else LL_SINCOS(dl, &sd, &cd);
+      double* o = su + kStageW * (k * C + c);
+      const double ua = a.U[2 * e];
+      const double p0 = k ? a.U[2 * e - 2] : a.uprev[0], p1 = k ? a.U[2 * e - 1] : a.uprev[1];
+      const double d0 = ua - p0, d1 = dl - p1;
+      if (INTEG == 0) {
+        const FusedIn fi = fused_in(fq0, Input{ua, dl, sd, cd});
+        o[0] = fi.F0;
+        o[1] = fi.F1;
+        o[2] = fi.hmsd;
+        o[3] = fi.hmcd;
+        o[4] = fi.c5a;
+        o[5] = dl;
+      } else {
+        o[0] = ua;
+        o[1] = dl;
+        o[2] = sd;
+        o[3] = cd;
+      }
+      o[6] = act_term(a.cost, d0, d1);
+      o[7] = (!a.cost.enforce || input_feasible(a.cost, ua, dl, d0, d1)) ? 1.0 : 0.0;
+    }
+  }
+  __syncthreads();
+
+  CostK q = a.cost;
+  VehK veh = a.veh;
+  double Ts = a.Ts;
+  for (int m = 0; m < 4; ++m) {
+    pin_vgpr(q.Q[m]);
+    pin_vgpr(q.R[m]);
+    pin_vgpr(q.P[m]);
+  }
+  for (int m = 0; m < 2; ++m) {
+    pin_vgpr(q.umin[m]);
+    pin_vgpr(q.umax[m]);
+    pin_vgpr(q.dmax[m]);
+  }
+  pin_vgpr(veh.lf);
+  pin_vgpr(veh.lr);
+  pin_vgpr(veh.mass);
+  pin_vgpr(veh.inv_mass);
+  pin_vgpr(veh.inv_Iz);
+  pin_vgpr(veh.Cm1);
+  pin_vgpr(veh.Cm2);
+  pin_vgpr(veh.Cr0);
+  pin_vgpr(veh.Cr2);
+  pin_vgpr(Ts);
+  const double up0 = a.uprev[0], up1 = a.uprev[1];
+
+  double bv = __builtin_nan("");
+  int64_t bc = kNoIndex;
+  int nf = 0;
+  LA_STAMP(blk, 1);
+  // position split of the quad (fused RK4, LPM = 4) when Q and P are diagonal (rt.py:60-62:
+  // Q = diag(1, 1), P = 0): tested on the unpinned kernel-argument copy, so the branch is
+  // scalar
+  constexpr bool kSplit = (INTEG == 0 && LPM == 4);
+  // the rollouts' variant: the re-run of bad lanes is kRF itself, the fast run adds kRFast
+  constexpr unsigned kRF = (STAGE ? kRStage : 0u) | (XM ? kRXm : 0u);
+  constexpr unsigned kRSplitQ = kSplit ? kRSplit : 0u;      // the quad's position split
+  const bool diagQP = a.cost.Q[1] == 0.0 && a.cost.Q[2] == 0.0 && a.cost.P[1] == 0.0 && a.cost.P[2] == 0.0;
+  if constexpr (WQ) {
+    static_assert(LPM == 1 && XM == 0, "work queue: LPM 1, shared xref");
+    // Unit u = models [u mpw, (u + 1) mpw) of one wave.  Lane 0 takes unit numbers from the
+    // bank's counter (relaxed agent-scope add; 0 at the launch's start: the block completing
+    // the record resets it in final_write, after every look-ahead block has published, i.e.
+    // after every take of the launch); the next take is issued before the current unit's
+    // rollouts and read after them, so its latency is hidden.  The counter only grows within
+    // a launch, so u >= 0 and every model index is checked against n.
+    const int mpw = 64 / G;
+    const int64_t units = (a.n + mpw - 1) / mpw;
+    const int lm = (int)(threadIdx.x & 63) / G;
+    // The take must stay in flight across the rollouts.  In v30 every unit waited for its
+    // round trip (ISA: s_waitcnt vmcnt(0) right after the atomic): the atomic optimizer
+    // rewrites an atomic on a uniform address into one lane's atomic plus a
+    // readfirstlane/prefix epilogue that uses the result at once.  So the address carries an
+    // opaque zero VGPR offset (not uniform to the compiler: no optimizer rewrite).  And with
+    // the row loads and the atomic both pending, the waitcnt pass cannot count them apart
+    // (a returning atomic and loads are different event kinds: it waits for vmcnt(0), i.e.
+    // for the atomic too, at the first use of the row); so the offset of each take is a zero
+    // that depends on the unit's Pacejka row (an asm reading the six values): the row is
+    // waited for first, then the atomic goes out and nothing waits for it until take().
+    uint32_t zoff;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zoff));
+    auto issue = [&](uint32_t off) -> uint64_t {
+      uint64_t v = 0;
+      if ((threadIdx.x & 63) == 0)
+        v = __hip_atomic_fetch_add(a.wq + off, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return v;
+    };
+    auto take = [&](uint64_t v) -> int64_t {
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 0);
+      const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 0);
+      return (int64_t)(((uint64_t)hi << 32) | lo);
+    };
+    double vacc = __builtin_nan("");
+    int64_t kacc = kNoIndex;
+    int nfacc = 0;
+    const fm::FmK K = K0;
+#ifdef LLAMPC_STAMPS
+    int ju = 0;                                             // this wave's unit count
+#endif
+    for (int64_t u = take(issue(zoff)); u < units;) {      // wave-uniform
+      WQ_STAMP(blk, ju, 0);
+      const int64_t nm = u * mpw + lm;
+      const bool lv = nm < a.n;
+      Tire tm{};
+      if (lv) tm = load_tire(a.params, a.n, nm);
+      uint32_t dep;
+      asm volatile("v_mov_b32 %0, 0" : "=v"(dep) : "v"(tm.Bf), "v"(tm.Cf), "v"(tm.Df), "v"(tm.Br), "v"(tm.Cr), "v"(tm.Dr));
+      WQ_STAMP(blk, ju, 1);
+      const uint64_t nxt = issue(dep);
+      double mv = __builtin_nan("");
+      int64_t mc = kNoIndex;
+      if (lv) {
+        constexpr bool kScaled = (INTEG == 0 && scaled_yaw(1));
+        StageK sk = make_stage<1>(veh, tm, 0, INTEG == 0 ? Ts : 1.0);
+        if (kScaled) {                  // the chains' lw / h turns W back into omega
+          sk.ch[0].lw = sk.ch[0].lw / Ts;
+          sk.ch[1].lw = sk.ch[1].lw / Ts;
+        }
+        const FusedK fq = make_fused(veh, sk, Ts, kScaled);
+        for (int j = 0; j < cpl; ++j) {
+          const int c = g + j * G;
+          if (c >= C) break;
+          bool bad = false;
+          double J = rollout<INTEG, 1, kRF | kRFast>(a, c, nm, x0, sx, su, veh, tm, sk, q, Ts, up0, up1, K, fq, bad);
+          if (__builtin_expect(__any(bad), 0)) {
+            bool unused = false;
+            if (bad) J = rollout<INTEG, 1, kRF>(a, c, nm, x0, sx, su, veh, tm, sk, q, Ts, up0, up1, K, fq, unused);
+          }
+          if (a.cost_out) a.cost_out[nm * C + c] = J;
+          nfacc += !isfinite(J);
+          if (less_nan_last(J, c, mv, mc)) {
+            mv = J;
+            mc = c;
+          }
+        }
+      }
+      for (int off = G >> 1; off >= 1; off >>= 1) {        // the model's argmin over its lanes
+        const double ov = __shfl_xor(mv, off, 64);
+        const int64_t oc = __shfl_xor(mc, off, 64);
+        if (less_nan_last(ov, oc, mv, mc)) {
+          mv = ov;
+          mc = oc;
+        }
+      }
+      WQ_STAMP(blk, ju, 2);
+      const int64_t un = take(nxt);                         // before the unit's stores
+      if (lv && g == 0) {
+        if (a.poll) {
+          st_wt(&a.la_tag[nm], tag_word(a.seq, (uint32_t)(__double_as_longlong(mv) >> 32)));
+          st_wt(&a.la_tag[a.n + nm], tag_word(a.seq, (uint32_t)__double_as_longlong(mv)));
+          st_wt(&a.la_tag[2 * a.n + nm], tag_word(a.seq, (uint32_t)(int32_t)mc));
+        } else {
+          st_wt(&a.best_cand[nm], (int32_t)mc);
+          st_wt(&a.best_cost[nm], mv);
+        }
+        if (mc != kNoIndex) {
+          const int64_t key = (a.goff + nm) * C + mc;
+          if (less_bf<0>(mv, key, vacc, kacc)) {
+            vacc = mv;
+            kacc = key;
+          }
+        }
+      }
+      WQ_STAMP(blk, ju, 3);
+#ifdef LLAMPC_STAMPS
+      ++ju;
+#endif
+      u = un;
+    }
+    LA_STAMP(blk, 2);
+    la_publish<BT / 64>(a, blk, sc, 0, vacc, kacc, nfacc);
+    LA_STAMP(blk, 3);
+    return;
+  }
+  if (live) {
+    // LPM = 2: lane 0 of the pair evaluates the front chain, lane 1 the rear (dyn.hpp)
+    // fused RK4 quads carry W = h omega and Psi = (2/pi) psi (make_fused): the chains'
+    // lw / h turns W back into omega
+    constexpr bool kScaled = (INTEG == 0 && scaled_yaw(LPM));
+    StageK sk = make_stage<LPM>(veh, t, sub, INTEG == 0 ? Ts : 1.0);
+    if (kScaled) sk.ch[0].lw = sk.ch[0].lw / Ts;
+    if (kScaled && LPM == 1) sk.ch[1].lw = sk.ch[1].lw / Ts;
+    if (kScaled && LPM == 4 && sub >= 2) {
+      // lanes 2/3 run their (discarded) chain on zero operands — yy = z = 0, no extra
+      // instruction: fewer toggling bits, a higher clock (A/B 28.86 -> 28.61 us/tick).
+      // (Freezing the unused yaw of lanes 0/1 as well, by per-lane RK4 weights 0: 28.98.)
+      sk.ch[0].lw = 0.0;
+      sk.ch[0].sg = 0.0;
+      sk.ch[0].B = 0.0;
+      sk.ch[0].nsB = 0.0;
+    }
+    const FusedK fq = make_fused(veh, sk, Ts, kScaled);
+    const fm::FmK K = [&] {
+      if constexpr (XM) return fm::FmK::load<kLeanLA && INTEG == 0>();
+      else return K0;
+    }();
+    for (int j = 0; j < cpl; ++j) {
+      const int c = g + j * G;
+      if (c >= C) break;
+      bool bad = false;
+      double J;
+      if (kSplit && diagQP)             // launch-uniform (kernel arguments)
+        J = rollout<INTEG, LPM, kRF | kRFast | kRSplitQ>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, bad);
+      else
+        J = rollout<INTEG, LPM, kRF | kRFast>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, bad);
+      if (LPM == 2) {                   // the pair shares one rollout: re-run both or neither
+        const int bi = bad;
+        bad = __builtin_amdgcn_mov_dpp(bi, kPair0, 0xF, 0xF, false) |
+              __builtin_amdgcn_mov_dpp(bi, kPair1, 0xF, 0xF, false);
+      } else if (LPM == 4) {            // the quad shares one rollout
+        int bi = bad;
+        bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX1, 0xF, 0xF, false);
+        bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX2, 0xF, 0xF, false);
+        bad = bi;
+      }
+      if (__builtin_expect(__any(bad), 0)) {
+        bool unused = false;
+        if (bad) J = rollout<INTEG, LPM, kRF>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, unused);
+      }
+      if (sub == 0) {
+        if (a.cost_out) a.cost_out[n * C + c] = J;
+        nf += !isfinite(J);
+      }
+      if (less_nan_last(J, c, bv, bc)) {
+        bv = J;
+        bc = c;
+      }
+    }
+  }
+  LA_STAMP(blk, 2);
+#ifdef LLAMPC_STAMPS
+  if ((threadIdx.x & 63) == 0 && blk < 1024) g_la_wave[blk][threadIdx.x >> 6] = __builtin_amdgcn_s_memrealtime();
+#endif
+  // per-model argmin over its candidates: xor-shuffles across the model's lanes inside a
+  // wave, then (a model spanning 2 or 4 waves: G*LPM in {128, 256}) across its waves in LDS
+  const int span = G * LPM;
+  for (int off = (span < 64 ? span : 64) >> 1; off >= LPM; off >>= 1) {
+    const double ov = __shfl_xor(bv, off, 64);
+    const int64_t oc = __shfl_xor(bc, off, 64);
+    if (less_nan_last(ov, oc, bv, bc)) {
+      bv = ov;
+      bc = oc;
+    }
+  }
+  int par = 0;
+  if (span > 64) {                                  // block-uniform
+    double* sv = sc.sv + 4 * par;
+    int64_t* si = sc.si + 4 * par;
+    par ^= 1;
+    if ((threadIdx.x & 63) == 0) {
+      sv[threadIdx.x >> 6] = bv;
+      si[threadIdx.x >> 6] = bc;
+    }
+    __syncthreads();
+    const int w0 = (int)(threadIdx.x / span) * (span / 64);
+    bv = sv[w0];
+    bc = si[w0];
+    for (int k = 1; k < span / 64; ++k) {
+      if (less_nan_last(sv[w0 + k], si[w0 + k], bv, bc)) {
+        bv = sv[w0 + k];
+        bc = si[w0 + k];
+      }
+    }
+  }
+  if (live && g == 0 && sub == 0) {
+    if (a.poll) {                       // tagged words only (SoA: coalesced rows); C = 1: the
+      // candidate is 0, so only the cost's two words (final_poll)
+      st_wt(&a.la_tag[n], tag_word(a.seq, (uint32_t)(__double_as_longlong(bv) >> 32)));
+      st_wt(&a.la_tag[a.n + n], tag_word(a.seq, (uint32_t)__double_as_longlong(bv)));
+      st_wt(&a.la_tag[2 * a.n + n], tag_word(a.seq, (uint32_t)(int32_t)bc));
+    } else {
+      st_wt(&a.best_cand[n], (int32_t)bc);
+      st_wt(&a.best_cost[n], bv);
+    }
+  }
+  // per-block argmin over (model, candidate) in flattened order (goff+n)*C + c
+  const int64_t key = (live && bc != kNoIndex && g == 0 && sub == 0) ? (a.goff + n) * C + bc : kNoIndex;
+  la_publish(a, blk, sc, par, (key == kNoIndex) ? __builtin_nan("") : bv, key, nf);
+  LA_STAMP(blk, 3);
+}
+
+}  // namespace llampc

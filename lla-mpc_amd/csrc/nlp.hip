@@ -31,8 +31,9 @@
 //                   helper waves 5-7 while waves 0-3 complete the round.  (A bitonic sort
 //                   of all samples in LDS took 36 us of the 62 us round: 55 barrier-separated
 //                   passes; the barrier-separated merge tree of round 6's first version 2.5 us.)
-#include "plan_dev.hpp"
+#include "dev_wave.hpp"
 #include "nlp.hpp"
+#include "rollout_dev.hpp"
 
 namespace llampc {
 
@@ -287,16 +288,15 @@ __device__ __forceinline__ void nlp_traj_quad(const NlpLaunch& a, const double* 
   double* out = sub == 0 ? &a.res->traj[0][0] : nullptr;
   if (sub == 0)
     for (int m = 0; m < 6; ++m) out[m] = x0[m];
+  constexpr unsigned kRF = kRUlds | kRTraj;                 // the re-run; the fast run adds kRFast
   bool bad = false;
-  (void)rollout<1, false, LPM, 0, true, false, true, true>(a.la, 0, 0, x0, sx, ub, veh, t, sk, q, Ts, a.up0, a.up1, K, fq,
-                                                           bad, out);
+  (void)rollout<1, LPM, kRF | kRFast>(a.la, 0, 0, x0, sx, ub, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad, out);
   int bi = bad;
   bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX1, 0xF, 0xF, false);
   bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX2, 0xF, 0xF, false);
   if (bi) {
     bool unused = false;
-    (void)rollout<1, false, LPM, 0, false, false, true, true>(a.la, 0, 0, x0, sx, ub, veh, t, sk, q, Ts, a.up0, a.up1, K,
-                                                              fq, unused, out);
+    (void)rollout<1, LPM, kRF>(a.la, 0, 0, x0, sx, ub, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused, out);
   }
 }
 
@@ -494,7 +494,7 @@ __device__ __forceinline__ void nlp_complete(const NlpLaunch& a, unsigned char* 
   __syncthreads();                      // ms (the next round's) and the LDS lists (the next poll)
 }
 
-// LDS words of nlp_complete32's hand-off between its waves (the scratch's pad, plan_dev.hpp
+// LDS words of nlp_complete32's hand-off between its waves (the scratch's pad, dev_wave.hpp
 // kScratchBytes): the Phase-A waves done (counted over the launch's rounds), a poll that timed
 // out, the round's best key and its sample.
 constexpr int kNlpDoneOff = 176, kNlpFailOff = 180, kNlpBestOff = 184, kNlpBestSOff = 164;
@@ -891,6 +891,7 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
     pin_vgpr(Ts);
     const StageK sk = make_stage<LPM>(veh, t, sub, 1.0);
     const FusedK fq = make_fused(veh, sk, Ts, false);
+    constexpr unsigned kRF = ST ? (kRStage | kRTraj) : kRUlds;   // the re-run; the fast run adds kRFast
     bool bad = false;
     double J;
     // the solve's last round: the sample's states after each step (the quad's lane 0, into LDS)
@@ -899,10 +900,9 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
     // round, in LDS or in global memory alike)
     double* tj = ST && a.ltraj && sub == 0 && it == a.iters - 1 ? trl + (size_t)c * 6 * H - 6 : nullptr;
     if constexpr (ST)
-      J = rollout<1, true, LPM, 0, true, false, false, true, false, false, kNlpStageW>(
-          a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad, tj);
+      J = rollout<1, LPM, kRF | kRFast, kNlpStageW>(a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad, tj);
     else
-      J = rollout<1, false, LPM, 0, true, false, true>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad);
+      J = rollout<1, LPM, kRF | kRFast>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad);
     int bi = bad;
     bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX1, 0xF, 0xF, false);
     bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX2, 0xF, 0xF, false);
@@ -910,11 +910,9 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
       bool unused = false;
       if (bi) {
         if constexpr (ST)
-          J = rollout<1, true, LPM, 0, false, false, false, true, false, false, kNlpStageW>(
-              a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused, tj);
+          J = rollout<1, LPM, kRF, kNlpStageW>(a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused, tj);
         else
-          J = rollout<1, false, LPM, 0, false, false, true>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K,
-                                                            fq, unused);
+          J = rollout<1, LPM, kRF>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused);
       }
     }
     NLP_STAMP(3);

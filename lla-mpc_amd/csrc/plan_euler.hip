@@ -1,5 +1,5 @@
 // plan_euler.hip — plan-kernel instantiations: the NLP Euler transcription, every lane split
-// (one translation unit per variant group; device code in plan_dev.hpp).
+// (one translation unit per variant group; the kernels in plan_dev.hpp, their device code in the *_dev.hpp role headers).
 #include "plan_dev.hpp"
 
 namespace llampc {

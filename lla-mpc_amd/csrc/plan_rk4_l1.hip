@@ -1,5 +1,5 @@
 // plan_rk4_l1.hip — plan-kernel instantiations: RK4, one lane per rollout (throughput regime, work-queue layouts) + its inline-pack host tick
-// (one translation unit per variant group; device code in plan_dev.hpp).
+// (one translation unit per variant group; the kernels in plan_dev.hpp, their device code in the *_dev.hpp role headers).
 #include "plan_dev.hpp"
 
 namespace llampc {

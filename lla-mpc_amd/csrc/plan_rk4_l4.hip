@@ -1,5 +1,5 @@
 // plan_rk4_l4.hip — plan-kernel instantiations: RK4, four lanes per rollout (the headline C = 1 tick) + its inline-pack host tick
-// (one translation unit per variant group; device code in plan_dev.hpp).
+// (one translation unit per variant group; the kernels in plan_dev.hpp, their device code in the *_dev.hpp role headers).
 #include "plan_dev.hpp"
 
 namespace llampc {

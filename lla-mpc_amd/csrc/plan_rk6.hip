@@ -1,5 +1,5 @@
 // plan_rk6.hip — plan-kernel instantiations: the RK6 plant integrator
-// (one translation unit per variant group; device code in plan_dev.hpp).
+// (one translation unit per variant group; the kernels in plan_dev.hpp, their device code in the *_dev.hpp role headers).
 #include "plan_dev.hpp"
 
 namespace llampc {
