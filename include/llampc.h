@@ -470,6 +470,19 @@ int llampc_nlp_create(llampc_bank* bank, const llampc_nlp_cfg* cfg, llampc_nlp**
  * -> umpc [H][2], fval, xmpc [H+1][6] (the Euler trajectory of umpc).  Blocking. */
 int llampc_nlp_solve(llampc_nlp* nlp, const double* x0, const double* xref, const double* uprev,
                      const double* base, int32_t has_hold, double* umpc, double* fval, double* xmpc);
+/* The same solve under a soft corridor: hp [H][6], row k - 1 = (a0, a1, b, c0, c1, d) the two
+ * half-planes a.p_k <= b and c.p_k <= d on the position p_k = (X, Y) after k Euler steps, k = 1..H
+ * (a = (0, 0), b = +inf disables one).  Every sample's objective becomes J + weight x pen, pen =
+ * sum_k max(a.p_k - b, 0)^2 + max(c.p_k - d, 0)^2 (k ascending, every product and sum rounded on
+ * its own); the bounds, the rate chain, the ranking and the warm start are llampc_nlp_solve's, and a
+ * corridor that no sample touches returns its umpc and fval bitwise.  fval includes the penalty;
+ * -> max_slack (may be NULL): the largest max(a.p_k - b, c.p_k - d, 0) along the returned xmpc.
+ * LLAMPC_E_ARG, with nothing launched: hp NULL, a non-finite normal component, an offset NaN or
+ * -inf, weight negative or non-finite.  hp travels through the solver's pinned mapped buffer.
+ * Blocking. */
+int llampc_nlp_solve_corridor(llampc_nlp* nlp, const double* x0, const double* xref, const double* uprev,
+                              const double* base, int32_t has_hold, const double* hp, double weight,
+                              double* umpc, double* fval, double* xmpc, double* max_slack);
 int llampc_nlp_destroy(llampc_nlp* nlp);
 
 /* ---- raw batched dynamics (Dynamic API parity) ---------------------------------- */

@@ -62,6 +62,38 @@ inline CostK make_cost(const llampc_cost& c, double Ts) {
   return k;
 }
 
+// A corridor hp [H][6] (llampc_nlp_solve_corridor: per step (a0, a1, b, c0, c1, d), a.p <= b and
+// c.p <= d) and its weight as the solve accepts them: finite normals, offsets finite or +inf (the
+// disabled half-plane's), a finite weight >= 0.  Null if valid, else what is wrong.
+inline const char* corridor_invalid(const double* hp, int32_t H, double weight) {
+  if (!(weight >= 0) || !std::isfinite(weight)) return "weight must be finite and >= 0";
+  for (int64_t k = 0; k < H; ++k) {
+    const double* r = hp + 6 * k;
+    if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[3]) || !std::isfinite(r[4]))
+      return "a normal component is not finite";
+    for (const double off : {r[2], r[5]})
+      if (std::isnan(off) || off == -HUGE_VAL) return "an offset is NaN or -inf (+inf disables a half-plane)";
+  }
+  return nullptr;
+}
+
+// The largest slack max_k max(s1, s2) of a trajectory xmpc [H+1][6] on the corridor: row k of hp
+// against the position after k + 1 steps, s = max(a.p - b, 0) in the device's order (rollout_dev.hpp
+// corridor_slack2), every product and sum rounded on its own.
+inline double corridor_max_slack(const double* hp, const double* xmpc, int32_t H) {
+#pragma clang fp contract(off)
+  double m = 0.0;
+  for (int64_t k = 0; k < H; ++k) {
+    const double* r = hp + 6 * k;
+    const double X = xmpc[6 * (k + 1)], Y = xmpc[6 * (k + 1) + 1];
+    const double g1 = (r[0] * X + r[1] * Y) - r[2];
+    const double g2 = (r[3] * X + r[4] * Y) - r[5];
+    if (g1 > m) m = g1;
+    if (g2 > m) m = g2;
+  }
+  return m;
+}
+
 // The polled completion's wait bound in s_memrealtime ticks (100 MHz): a 2 s floor plus
 // 40 ns per look-ahead rollout step of the launch (a rate floor of 2.5e7 steps/s, ~10^3
 // below the fast path's, so the general-path re-runs, the raceline walker and launches

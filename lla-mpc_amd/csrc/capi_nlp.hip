@@ -1,6 +1,8 @@
 // capi_nlp.hip — the setupNLP.solve drop-in's host side (llampc_nlp_*, include/llampc.h;
 // nlp.hip): CEM iterations enqueued back to back on the bank's stream, the Euler trajectory of
-// the best sequence, the result through pinned host memory.
+// the best sequence, the result through pinned host memory.  The corridor solve
+// (llampc_nlp_solve_corridor) is the same solve with the half-planes handed over in a pinned mapped
+// buffer and the largest slack of the returned trajectory computed here on the host.
 #include "capi_common.hpp"
 
 using namespace llampc;
@@ -21,6 +23,10 @@ struct __attribute__((visibility("hidden"))) llampc_nlp {
   bool ltraj = false;                    // the last round keeps its states in LDS (NlpLaunch.ltraj;
                                          // LLAMPC_NLP_RERUN_TRAJ=1 at create: always re-run, tests)
   MappedRecord<NlpResult> host;          // the last round writes the result, then the solve's number
+  Mapped<double> hp;                     // the corridor solve's half-planes [HMAX][6] (NlpCorridor.hp):
+                                         // pinned and mapped, written by the host before the launch,
+                                         // read once per block and launch (no H2D copy)
+  bool ltraj_cor = false;                // ltraj of a corridor solve (its LDS holds the half-planes too)
   uint64_t calls = 0;
   std::mutex mu;
 };
@@ -57,7 +63,8 @@ int llampc_nlp_create(llampc_bank* b, const llampc_nlp_cfg* cfg, llampc_nlp** ou
   // the lists: 3 words per entry, samples / 64 x len <= samples entries; both by round parity.
   // Tagged words start at tag 0, which no solve uses (nlp_seq of a solve number >= 1)
   if ((rc = p->d_st.zalloc(1)) || (rc = p->d_cost.zalloc((size_t)k.samples * (6 + 4 * H))) ||
-      (rc = p->d_ms_tag.zalloc(8 * (size_t)LLAMPC_HMAX)) || (rc = p->host.alloc("NLP result")))
+      (rc = p->d_ms_tag.zalloc(8 * (size_t)LLAMPC_HMAX)) || (rc = p->host.alloc("NLP result")) ||
+      (rc = p->hp.alloc(6 * (size_t)LLAMPC_HMAX, "NLP corridor")))
     return rc;
   {
     // every round in one launch needs all samples / 64 blocks resident together (each waits for
@@ -68,6 +75,7 @@ int llampc_nlp_create(llampc_bank* b, const llampc_nlp_cfg* cfg, llampc_nlp** ou
     p->per_round = !nlp_persistent(k.samples) || !resident || (e && e[0] == '1');
     const char* rt = std::getenv("LLAMPC_NLP_RERUN_TRAJ");
     p->ltraj = nlp_ltraj_fits(k.H, k.samples, k.elite) && !(rt && rt[0] == '1');
+    p->ltraj_cor = nlp_corridor_ltraj_fits(k.H, k.samples, k.elite) && !(rt && rt[0] == '1');
   }
   if (hipDeviceSynchronize() != hipSuccess)
     return fail(LLAMPC_E_HIP, "NLP solver upload failed");
@@ -75,9 +83,13 @@ int llampc_nlp_create(llampc_bank* b, const llampc_nlp_cfg* cfg, llampc_nlp** ou
   return LLAMPC_OK;
 }
 
-int llampc_nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const double* uprev, const double* base,
-                     int32_t has_hold, double* umpc, double* fval, double* xmpc) {
-  if (!p || !x0 || !xref || !uprev || !umpc) return fail(LLAMPC_E_ARG, "NULL argument");
+}  // extern "C"
+
+// One solve: the unconstrained search (hp null: llampc_nlp_solve) or the corridor's (hp [H][6]
+// and its weight, checked by the caller: llampc_nlp_solve_corridor).
+static int nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const double* uprev, const double* base,
+                     int32_t has_hold, const double* hp, double weight, double* umpc, double* fval, double* xmpc,
+                     double* max_slack) {
   std::lock_guard<std::mutex> lp(p->mu);
   llampc_bank* b = p->b;
   std::lock_guard<std::mutex> lk(b->mu);
@@ -87,6 +99,17 @@ int llampc_nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
   const llampc_nlp_cfg& k = p->cfg;
   const int H = k.H;
   hipStream_t s = b->stream;
+  NlpCorridor cor{};
+  if (hp) {
+    if (nlp_corridor_lds_bytes(H, k.samples, k.elite) > 160 * 1024)
+      return fail(LLAMPC_E_ARG, "H x elite too large for LDS with a corridor");
+    std::memcpy(p->hp.get(), hp, 6 * (size_t)H * sizeof(double));
+    cor.hp = p->hp.dev();
+    cor.weight = weight;
+  }
+  auto launch = [&](const NlpLaunch& a, const NlpInline& pk) {
+    return hp ? launch_nlp_corridor(a, pk, cor, s) : launch_nlp(a, pk, s);
+  };
   // the launch's inputs (NlpInline): x0, xref, the first mean (base or uprev held); the first
   // std is sigma0, the best so far starts at +inf (the kernel's round 0)
   NlpInline pk;
@@ -111,7 +134,7 @@ int llampc_nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
   a.host_tag = p->host.tag.dev();
   a.host_seq = p->calls + 1;
   a.ms_tag = p->d_ms_tag.get();
-  a.ltraj = p->ltraj;
+  a.ltraj = hp ? p->ltraj_cor : p->ltraj;
   a.seed = k.seed;
   a.call = p->calls;
   a.up0 = uprev[0];
@@ -137,13 +160,13 @@ int llampc_nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
     for (int it = 0; it < k.iters; ++it) {
       a.it = it;
       TimedLaunch tl(b, 0, s);           // llampc_bank_timing on the solver's bank: per round
-      HIP_TRY(launch_nlp(a, pk, s));
+      HIP_TRY(launch(a, pk));
     }
   } else {                              // every round in one launch (nlp.hpp nlp_persistent)
     a.it = 0;
     a.rounds = k.iters;
     TimedLaunch tl(b, 0, s);             // llampc_bank_timing on the solver's bank: per solve
-    HIP_TRY(launch_nlp(a, pk, s));
+    HIP_TRY(launch(a, pk));
   }
   // the last round's completion writes the result into pinned memory and then the tag
   const uint64_t want = p->calls + 1;
@@ -166,8 +189,26 @@ int llampc_nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
     for (int j = 0; j < 2; ++j) umpc[2 * i + j] = r->best_u[i][j];
   if (fval) *fval = r->best_j;
   if (xmpc) std::memcpy(xmpc, &r->traj[0][0], 6 * (size_t)(H + 1) * sizeof(double));
+  if (hp && max_slack) *max_slack = corridor_max_slack(hp, &r->traj[0][0], H);
   if (r->best_it < 0) return fail(LLAMPC_E_DEVICE, "no finite objective in %d rounds of %d samples", k.iters, k.samples);
   return LLAMPC_OK;
+}
+
+extern "C" {
+
+int llampc_nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const double* uprev, const double* base,
+                     int32_t has_hold, double* umpc, double* fval, double* xmpc) {
+  if (!p || !x0 || !xref || !uprev || !umpc) return fail(LLAMPC_E_ARG, "NULL argument");
+  return nlp_solve(p, x0, xref, uprev, base, has_hold, nullptr, 0.0, umpc, fval, xmpc, nullptr);
+}
+
+int llampc_nlp_solve_corridor(llampc_nlp* p, const double* x0, const double* xref, const double* uprev,
+                              const double* base, int32_t has_hold, const double* hp, double weight, double* umpc,
+                              double* fval, double* xmpc, double* max_slack) {
+  if (!p || !x0 || !xref || !uprev || !umpc) return fail(LLAMPC_E_ARG, "NULL argument");
+  if (!hp) return fail(LLAMPC_E_ARG, "hp is NULL (llampc_nlp_solve is the unconstrained solve)");
+  if (const char* why = corridor_invalid(hp, p->cfg.H, weight)) return fail(LLAMPC_E_ARG, "corridor: %s", why);
+  return nlp_solve(p, x0, xref, uprev, base, has_hold, hp, weight, umpc, fval, xmpc, max_slack);
 }
 
 }  // extern "C"

@@ -31,6 +31,10 @@
 //                   helper waves 5-7 while waves 0-3 complete the round.  (A bitonic sort
 //                   of all samples in LDS took 36 us of the 62 us round: 55 barrier-separated
 //                   passes; the barrier-separated merge tree of round 6's first version 2.5 us.)
+//
+// The corridor solve (llampc_nlp_solve_corridor) is the same kernel with one more argument
+// (NlpCorridor): per-step position half-planes in LDS, their squared slacks added to every
+// sample's objective in the rollout (rollout_dev.hpp kRCorr); nothing else of the search changes.
 #include "dev_wave.hpp"
 #include "nlp.hpp"
 #include "rollout_dev.hpp"
@@ -738,7 +742,8 @@ __device__ __forceinline__ void nlp_draw(const NlpLaunch& a, int blk, int it, do
 // then free of bank conflicts; 2 H unstaged, the rollouts' layout) | x0 [6] | keys [64] | mean /
 // std [2][H][2] | the best sequence so far [H][2] | ST: the staged terms [H][64][kNlpStageW] — the completion's region
 // (nlp_comp_bytes) reuses them once the rollouts are done — else the completion's region |
-// ltraj: the samples' rollout states [64][H][6] (nlp_traj_off).
+// the corridor solve: its half-planes [H][6] (nlp_traj_off) | ltraj: the samples' rollout states
+// [64][H][6] (at nlp_traj_off in the unconstrained solve).
 __host__ __device__ __forceinline__ size_t nlp_su_off(int H) {
   return kScratchBytes + 16 * (size_t)(H + 1) + 8 * 64 * (2 * (size_t)H + 1) + 48 + 8 * 64 + 48 * (size_t)H;
 }
@@ -751,8 +756,17 @@ __host__ __device__ __forceinline__ size_t nlp_traj_off(int H, int nl, int elite
 // NT threads: the rollouts take the first 256 (a quad per sample); the other waves share the
 // blocks' per-round loops (bounds, staging, the completion) and draw the next round's variates
 // while the rollouts run (ST), two waves per SIMD
-template <bool ST, int NT>
-__global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
+// Cor: empty (the unconstrained solve: its arguments and its code are what they were before the
+// corridor existed) or one NlpCorridor, the corridor solve's own argument (COR): the half-planes hp
+// [H][6] copied once per launch into the block's LDS (48 H bytes at nlp_traj_off, the kept states
+// after them), the rollouts' objective with the corridor term (rollout_dev.hpp kRCorr).
+__device__ __forceinline__ NlpCorridor nlp_cor() { return NlpCorridor{nullptr, 0.0}; }
+__device__ __forceinline__ NlpCorridor nlp_cor(NlpCorridor c) { return c; }
+template <bool ST, int NT, class... Cor>
+__global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk, Cor... corv) {
+  constexpr bool COR = sizeof...(Cor) == 1;
+  static_assert(sizeof...(Cor) <= 1, "at most the corridor's argument");
+  [[maybe_unused]] const NlpCorridor cor = nlp_cor(corv...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int* rflag = reinterpret_cast<int*>(smem + kFlagOff);   // a bounded wait's block verdict
   const int tid = threadIdx.x, H = a.H, blk = (int)blockIdx.x;
@@ -767,7 +781,8 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
   double* bu = ms + 4 * H;                                                  // the best sequence so far [H][2]
   double* su = reinterpret_cast<double*>(smem + nlp_su_off(H));             // ST: [H][64][kNlpStageW]
   unsigned char* cbase = smem + nlp_su_off(H);                              // the completion's region
-  double* trl = reinterpret_cast<double*>(smem + nlp_traj_off(H, nl, a.elite));   // ltraj: [64][H][6]
+  double* shp = reinterpret_cast<double*>(smem + nlp_traj_off(H, nl, a.elite));   // COR: hp [H][6]
+  double* trl = COR ? shp + 6 * H : shp;                                           // ltraj: [64][H][6]
   NlpState* st = a.st;
   const int len = nlp_list_len(a.elite), nbl = nl * len;
   const double* xin = pk.v;             // the inputs in the kernarg segment (NlpInline)
@@ -781,7 +796,18 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
     sx[2 * e + 1] = xin[6 + (H + 1) + e];
   }
   if (tid < 6) x0[tid] = xin[tid];
+  // the corridor from host memory: the loads in flight while the first variates are drawn
+  static_assert(!COR || 2 * NT >= 6 * LLAMPC_HMAX, "the corridor's copy: at most two doubles per thread");
+  [[maybe_unused]] double hv0 = 0.0, hv1 = 0.0;
+  if constexpr (COR) {
+    if (tid < 6 * H) hv0 = cor.hp[tid];
+    if (tid + NT < 6 * H) hv1 = cor.hp[tid + NT];
+  }
   nlp_draw(a, blk, a.it, Ul, us, tid, NT);   // the first round's variates
+  if constexpr (COR) {                  // read by the rollouts, after the round's barriers
+    if (tid < 6 * H) shp[tid] = hv0;
+    if (tid + NT < 6 * H) shp[tid + NT] = hv1;
+  }
   // the best so far as the launch starts (none, or an earlier launch's rounds)
   double bjv = nlp_uni(a.it == 0 ? HUGE_VAL : ld_wt(&st->best_j));
   int bitv = __builtin_amdgcn_readfirstlane(a.it == 0 ? -1 : ld_wt(&st->best_it));
@@ -891,7 +917,8 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
     pin_vgpr(Ts);
     const StageK sk = make_stage<LPM>(veh, t, sub, 1.0);
     const FusedK fq = make_fused(veh, sk, Ts, false);
-    constexpr unsigned kRF = ST ? (kRStage | kRTraj) : kRUlds;   // the re-run; the fast run adds kRFast
+    constexpr unsigned kRF = (ST ? (kRStage | kRTraj) : kRUlds) | (COR ? kRCorr : 0u);   // the re-run; the fast run adds kRFast
+    [[maybe_unused]] const double cw = COR ? cor.weight : 0.0;
     bool bad = false;
     double J;
     // the solve's last round: the sample's states after each step (the quad's lane 0, into LDS)
@@ -900,9 +927,11 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
     // round, in LDS or in global memory alike)
     double* tj = ST && a.ltraj && sub == 0 && it == a.iters - 1 ? trl + (size_t)c * 6 * H - 6 : nullptr;
     if constexpr (ST)
-      J = rollout<1, LPM, kRF | kRFast, kNlpStageW>(a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad, tj);
+      J = rollout<1, LPM, kRF | kRFast, kNlpStageW>(a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad, tj,
+                                                    nullptr, nullptr, 0, nullptr, shp, cw);
     else
-      J = rollout<1, LPM, kRF | kRFast>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad);
+      J = rollout<1, LPM, kRF | kRFast>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad, nullptr,
+                                        nullptr, nullptr, 0, nullptr, shp, cw);
     int bi = bad;
     bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX1, 0xF, 0xF, false);
     bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX2, 0xF, 0xF, false);
@@ -910,9 +939,11 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk) {
       bool unused = false;
       if (bi) {
         if constexpr (ST)
-          J = rollout<1, LPM, kRF, kNlpStageW>(a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused, tj);
+          J = rollout<1, LPM, kRF, kNlpStageW>(a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused, tj,
+                                           nullptr, nullptr, 0, nullptr, shp, cw);
         else
-          J = rollout<1, LPM, kRF>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused);
+          J = rollout<1, LPM, kRF>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused, nullptr,
+                                   nullptr, nullptr, 0, nullptr, shp, cw);
       }
     }
     NLP_STAMP(3);
@@ -983,6 +1014,28 @@ hipError_t launch_nlp(const NlpLaunch& a, const NlpInline& pk, hipStream_t s) {
   } else {
     allow_lds(nlp_kernel<false, kBlock>);
     hipLaunchKernelGGL((nlp_kernel<false, kBlock>), grid, dim3(kBlock), lds, s, a, pk);
+  }
+  return hipGetLastError();
+}
+
+// The corridor solve sizes its own LDS: the unconstrained layout with the half-planes [H][6]
+// before the kept states, which it drops (the re-run trajectory) when they no longer fit.
+size_t nlp_corridor_lds_bytes(int H, int samples, int elite, bool ltraj) {
+  return nlp_lds_bytes(H, samples, elite, ltraj) + 48 * (size_t)H;
+}
+bool nlp_corridor_ltraj_fits(int H, int samples, int elite) {
+  return H <= kNlpStageH && nlp_corridor_lds_bytes(H, samples, elite, true) <= 160 * 1024;
+}
+
+hipError_t launch_nlp_corridor(const NlpLaunch& a, const NlpInline& pk, const NlpCorridor& cor, hipStream_t s) {
+  const size_t lds = std::max<size_t>(nlp_corridor_lds_bytes(a.H, a.samples, a.elite, a.ltraj != 0), 82 * 1024);
+  const dim3 grid(a.samples / 64);      // as launch_nlp
+  if (a.H <= kNlpStageH) {
+    allow_lds(nlp_kernel<true, 2 * kBlock, NlpCorridor>);
+    hipLaunchKernelGGL((nlp_kernel<true, 2 * kBlock, NlpCorridor>), grid, dim3(2 * kBlock), lds, s, a, pk, cor);
+  } else {
+    allow_lds(nlp_kernel<false, kBlock, NlpCorridor>);
+    hipLaunchKernelGGL((nlp_kernel<false, kBlock, NlpCorridor>), grid, dim3(kBlock), lds, s, a, pk, cor);
   }
   return hipGetLastError();
 }

@@ -90,4 +90,18 @@ size_t nlp_lds_bytes(int H, int samples, int elite, bool ltraj = false);
 bool nlp_ltraj_fits(int H, int samples, int elite);
 hipError_t launch_nlp(const NlpLaunch& a, const NlpInline& pk, hipStream_t s);
 
+// The corridor solve's own argument (llampc_nlp_solve_corridor): the unconstrained kernels'
+// arguments stay as they are.  hp [H][6]: per step k = 1..H the half-planes (a0, a1, b, c0, c1, d),
+// a.p_k <= b and c.p_k <= d on the position after k Euler steps (rollout_dev.hpp
+// corridor_slack2); the device alias of the solver's pinned mapped buffer — 48 H bytes do not fit
+// the kernarg segment beside NlpInline — which each block copies once per launch into its LDS
+// (after the region nlp_traj_off starts, before the kept states).  weight: J + weight x pen.
+struct NlpCorridor {
+  const double* hp;
+  double weight;
+};
+size_t nlp_corridor_lds_bytes(int H, int samples, int elite, bool ltraj = false);
+bool nlp_corridor_ltraj_fits(int H, int samples, int elite);   // else the re-run trajectory
+hipError_t launch_nlp_corridor(const NlpLaunch& a, const NlpInline& pk, const NlpCorridor& cor, hipStream_t s);
+
 }  // namespace llampc

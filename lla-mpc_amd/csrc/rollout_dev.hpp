@@ -36,6 +36,26 @@ __device__ __forceinline__ bool input_feasible(const CostK& q, double ua, double
          ((int)(q.dmax[1] < 0) | (int)(fabs(d1) <= q.dmax[1]));
 }
 
+// The corridor term of one step (CORR): hp = (a0, a1, b, c0, c1, d), the half-planes a.p <= b and
+// c.p <= d on the position p = (X, Y) after the step; the squared slacks s1^2 + s2^2, every
+// product and sum rounded on its own.  a = 0, b = +inf disables a half-plane (g = -inf, s = 0;
+// so does a NaN g: the comparison is false).
+__device__ __forceinline__ double corridor_slack2(const double* hp, double X, double Y) {
+#pragma clang fp contract(off)
+  const double2 r0 = *reinterpret_cast<const double2*>(hp);
+  const double2 r1 = *reinterpret_cast<const double2*>(hp + 2);
+  const double2 r2 = *reinterpret_cast<const double2*>(hp + 4);
+  const double g1 = (r0.x * X + r0.y * Y) - r1.x;
+  const double g2 = (r1.y * X + r2.x * Y) - r2.y;
+  const double s1 = g1 > 0 ? g1 : 0.0, s2 = g2 > 0 ? g2 : 0.0;
+  return s1 * s1 + s2 * s2;
+}
+__device__ __forceinline__ double corridor_add(double J, double cw, double pen) {
+#pragma clang fp contract(off)
+  const double wp = cw * pen;
+  return J + wp;
+}
+
 // The rollout's compile-time variants: the template argument F of rollout is an OR of these.
 enum RolloutFlag : unsigned {
   kRStage = 1u << 0,  // STAGE: the inputs staged per block at `su` as [k][c][SW] records (lookahead_block, nlp.hip)
@@ -48,6 +68,8 @@ enum RolloutFlag : unsigned {
   kRTraj = 1u << 5,   // TRAJ: the state after every step to `traj` (three 16-B stores; null: none)
   kRS4 = 1u << 6,     // S4 (ctl.hip ctl_stage, with ULDS and FAST): sin / cos delta and the cost terms read at `s4`
   kRDefer = 1u << 7,  // DEFER (ctl.hip ctl_spec, with SPLIT and S4): positions to `dpos`, the rest to *dout
+  kRCorr = 1u << 8,   // CORR (nlp.hip's corridor solve): two position half-planes per step at `hp` [H][6] (LDS), the
+                      //   squared slacks summed over the horizon, J + cw pen (corridor_slack2 below)
 };
 // What DEFER returns in *dout: the reference is not known yet, so the lane stores its position
 // component after step k at dpos[k dstride] instead of accumulating the tracking term, and
@@ -71,15 +93,18 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
                                           double Ts, double up0, double up1, const fm::FmK& K,
                                           const FusedK& fq, bool& bad, double* traj = nullptr,
                                           const double* s4 = nullptr, double* dpos = nullptr, int dstride = 0,
-                                          DeferOut* dout = nullptr) {
+                                          DeferOut* dout = nullptr, const double* hp = nullptr,
+                                          double cw = 0.0) {
   constexpr bool STAGE = F & kRStage, FAST = F & kRFast, SPLIT = F & kRSplit, ULDS = F & kRUlds;
-  constexpr bool TRAJ = F & kRTraj, S4 = F & kRS4, DEFER = F & kRDefer;
+  constexpr bool TRAJ = F & kRTraj, S4 = F & kRS4, DEFER = F & kRDefer, CORR = F & kRCorr;
   constexpr int XM = (F & kRXm) ? 1 : 0;
   static_assert(!DEFER || (SPLIT && S4), "deferred tracking cost: the controller's split, staged rollout");
   static_assert(!TRAJ || (INTEG != 0 && !SPLIT), "trajectory output: unscaled, unsplit state");
   static_assert(!S4 || (ULDS && FAST && !STAGE), "staged sincos / cost terms: the controller's fast rollout");
   static_assert(!SPLIT || (FAST && INTEG == 0 && LPM == 4), "position split: fused RK4 quads only");
   static_assert(!ULDS || !STAGE, "candidates in LDS: unstaged rollout");
+  static_assert(!CORR || (!SPLIT && !DEFER), "corridor term: a lane that holds both position components");
+  static_assert(!CORR || (INTEG == 1 && LPM == 4 && !S4 && !XM), "corridor term: built for the NLP kernel's rollouts");
   const int H = a.H, C = a.C;
   const double* Ub = ULDS ? su : a.U;
   double x[6];
@@ -96,6 +121,7 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
   bool feas = true;
   double feas_s = 1.0;
   double xr0 = 0.0, xr1 = 0.0;
+  [[maybe_unused]] double pen = 0.0;    // CORR: the summed squared slacks
   const double* xpm = XM ? a.xref_pm + n * 2 * H : nullptr;   // this model's reference
   Dom dm;                               // FAST: the operands' running extremes
   dm.init();
@@ -147,6 +173,7 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
     else if (FAST && INTEG == 0) step_fused<LPM, SPLIT>(sk, fq, x, u, K, dm);
     else if (FAST) step_fast<INTEG, LPM>(veh, t, sk, x, u, Ts, K, dm);
     else step<INTEG>(veh, t, x, u, Ts);
+    if constexpr (CORR) pen = pen + corridor_slack2(hp + 6 * k, x[0], x[1]);
     if (DEFER) {                        // the position component, for defer_cost
       dpos[k * dstride] = x[0];
     } else if (SPLIT) {                 // this lane's component of the reference and term
@@ -194,6 +221,7 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
     const double term = e0 * (q.P[0] * e0 + q.P[1] * e1) + e1 * (q.P[2] * e0 + q.P[3] * e1);
     J = (term + track) + act;                                     // nmpc.py:111
   }
+  if constexpr (CORR) J = corridor_add(J, cw, pen);
   // the domain, once per rollout: a NaN operand reaches x[0..1] (every chain output feeds
   // the later stages' positions, the last stage's feeds vx, vy, omega only through a NaN
   // state that the position update already carries), so a non-finite J is re-run too

@@ -17,9 +17,20 @@ mean and spread), the result comes back through pinned host memory.  Every retur
 ``umpc`` satisfies the NLP's bounds and rate constraints; ``fval`` is the objective of
 ``umpc`` and ``xmpc`` its Euler trajectory — the same triple IPOPT's feasible point would give.
 
+A *corridor* keeps the search on the track: ``solve(x0, xref, uprev, corridor=hp)`` with ``hp``
+[H, 6], row k - 1 = (a0, a1, b, c0, c1, d) the half-planes a.p_k <= b and c.p_k <= d on the
+position p_k after k Euler steps (a = 0, b = +inf disables one).  Every sample's objective gains
+``corridor_weight`` x sum_k max(a.p_k - b, 0)^2 + max(c.p_k - d, 0)^2 (a soft constraint, evaluated
+in the rollout on the device: llampc_nlp_solve_corridor); ``fval`` includes it, and the fourth
+return value is ``Ts`` if the largest slack along ``xmpc`` (``self.max_slack``) exceeds
+``corridor_tol`` (1e-4, IPOPT's constr_viol_tol), else 0.0.  ``llampc.mpc.constraints`` builds
+corridors: ``track_corridor(track, xref)`` from a track's centre line and width, ``strip`` around
+any polyline.  ``corridor=None`` is the unconstrained solve, unchanged.
+
 ``track_cons=True`` (rt.py:63 uses False everywhere) would add the track-boundary half-planes
-of constraints.py; the boundary lines are packaged (llampc.tracks) but the constraint is not
-implemented here (out of scope): it raises.
+of constraints.py with the reference's own linearisation and slack variables, which cannot be
+restated here (constraints.py is not available): it raises, and points to
+``corridor=``.
 """
 from __future__ import annotations
 
@@ -41,10 +52,17 @@ class setupNLP:
     """Same constructor and ``solve`` contract as nmpc.py:14-203 (see module doc)."""
 
     def __init__(self, horizon, Ts, Q, P, R, params, model, track, track_cons=False,
-                 samples=1024, iters=8, elite=32, sigma=(0.3, 0.15), std_floor=1e-4, seed=0, device=0):
+                 samples=1024, iters=8, elite=32, sigma=(0.3, 0.15), std_floor=1e-4, seed=0, device=0,
+                 corridor_weight=1e4, corridor_tol=1e-4):
         if track_cons:
             raise NotImplementedError("track_cons=True (constraints.py boundary half-planes) is not "
-                                      "implemented: the reference's LLA-MPC runs use TRACK_CONS=False (rt.py:63)")
+                                      "implemented: the reference's LLA-MPC runs use TRACK_CONS=False (rt.py:63); "
+                                      "pass solve(..., corridor=llampc.mpc.constraints.track_corridor(track, xref)) "
+                                      "for soft track half-planes in the device search")
+        self.corridor_weight, self.corridor_tol = float(corridor_weight), float(corridor_tol)
+        if not (np.isfinite(self.corridor_weight) and self.corridor_weight >= 0):
+            raise ValueError("corridor_weight must be finite and >= 0")
+        self.max_slack = 0.0         # the last corridor solve's largest slack along xmpc
         self.horizon, self.Ts = int(horizon), float(Ts)
         self.params, self.model, self.track, self.track_cons = params, model, track, track_cons
         self.samples, self.iters, self.elite = int(samples), int(iters), int(elite)
@@ -92,11 +110,18 @@ class setupNLP:
         self.cfg = cfg
         H = self.horizon
         self._io = {"x0": np.zeros(6), "xref": np.zeros((2, H + 1)), "up": np.zeros(2), "base": np.zeros((H, 2)),
-                    "umpc": np.zeros((H, 2)), "fval": np.zeros(1), "xmpc": np.zeros((H + 1, 6))}
+                    "umpc": np.zeros((H, 2)), "fval": np.zeros(1), "xmpc": np.zeros((H + 1, 6)),
+                    "hp": np.zeros((H, 6)), "slack": np.zeros(1)}
         self._addr = {k: v.ctypes.data for k, v in self._io.items()}
 
-    def solve(self, x0, xref, uprev):
-        """-> (umpc [2, H], fval, xmpc [6, H+1], violation in {0, 0.02}) as nmpc.py:161-203."""
+    def solve(self, x0, xref, uprev, corridor=None):
+        """-> (umpc [2, H], fval, xmpc [6, H+1], violation in {0, Ts}) as nmpc.py:161-203.
+        corridor: None, or the half-planes [H, 6] (module doc); violation is then Ts if the largest
+        slack along xmpc exceeds corridor_tol."""
+        if corridor is not None:
+            corridor = np.asarray(corridor, dtype=np.float64)
+            if corridor.shape != (self.horizon, 6):
+                raise ValueError(f"corridor must be [H, 6] = {(self.horizon, 6)}, got {corridor.shape}")
         self._ensure()
         b = self._io
         H = self.horizon
@@ -110,11 +135,21 @@ class setupNLP:
             b["base"][:-1] = self._last[1:]
             b["base"][-1] = self._last[-1]
         a = self._addr
-        nat.check(nat.load().llampc_nlp_solve(self._h, a["x0"], a["xref"], a["up"], a["base"] if hold else None,
-                                               int(hold), a["umpc"], a["fval"], a["xmpc"]))
+        violation = 0.0
+        if corridor is None:
+            nat.check(nat.load().llampc_nlp_solve(self._h, a["x0"], a["xref"], a["up"], a["base"] if hold else None,
+                                                   int(hold), a["umpc"], a["fval"], a["xmpc"]))
+        else:
+            b["hp"][:] = corridor
+            nat.check(nat.load().llampc_nlp_solve_corridor(self._h, a["x0"], a["xref"], a["up"],
+                                                            a["base"] if hold else None, int(hold), a["hp"],
+                                                            self.corridor_weight, a["umpc"], a["fval"], a["xmpc"],
+                                                            a["slack"]))
+            self.max_slack = float(b["slack"][0])
+            violation = self.Ts if self.max_slack > self.corridor_tol else 0.0
         umpc = b["umpc"].copy()
         self._last = umpc
-        return umpc.T.copy(), float(b["fval"][0]), b["xmpc"].T.copy(), 0.0
+        return umpc.T.copy(), float(b["fval"][0]), b["xmpc"].T.copy(), violation
 
     def close(self):
         if self._h is not None:

@@ -1,7 +1,8 @@
 """Diagnostic (build-time): VALU+SALU instructions per H-step of the fast look-ahead rollout
 loop for each lane split (LPM 1/2/4) of plan_kernel<RK4, staged, LPM, xref shared> and of the
-controller tick's ctl_kernel<LPM> (candidates in LDS, input terms staged: the shortest loop), from hipcc -S listings of the
-translation units that hold them.  bench.py's ISSUE_INSTR_PER_STEP holds the plan numbers.
+controller tick's ctl_kernel<LPM> (candidates in LDS, input terms staged: the shortest loop), and of
+the NLP kernel's Euler rollout (nlp_kernel<staged>, LPM 4) without and with the corridor term, from
+hipcc -S listings of the translation units that hold them.  bench.py's ISSUE_INSTR_PER_STEP holds the plan numbers.
 usage: python tools/diag/isa_counts.py [extra hipcc flags, e.g. -DLLAMPC_LEAN_TERMS=7]"""
 import collections
 import os
@@ -22,7 +23,7 @@ def listing(tu):
     return open(out).read().split("\n")
 
 
-def loop_of(asm, pattern, fmin=150, rcp=1):
+def loop_of(asm, pattern, fmin=150, rcp=1, nmin=200):
     s = next(i for i, l in enumerate(asm) if re.match(pattern, l))
     e = next(i for i in range(s, len(asm)) if "s_endpgm" in asm[i])
     body = asm[s:e]
@@ -35,7 +36,7 @@ def loop_of(asm, pattern, fmin=150, rcp=1):
             n = sum(1 for x in seg if re.match(r"^\s+(v_|s_)", x))
             f = sum(1 for x in seg if re.match(r"^\s+v_\w+_f64", x))
             # the rollout step: the innermost loop with the division and most fp64 work
-            if sum("v_rcp_f64" in x for x in seg) >= rcp and 200 < n < 2000 and f > fmin and (best is None or n < best[0]):
+            if sum("v_rcp_f64" in x for x in seg) >= rcp and nmin < n < 2000 and f > fmin and (best is None or n < best[0]):
                 best = (n, seg)
     return best
 
@@ -64,3 +65,10 @@ for lpm in (4, 2, 1):
     # a whole RK4 step: 4 stages x 2 chains' divisions (the look-back's and the walker's loops
     # divide too)
     report(f"ctl LPM {lpm} (staged inputs)", loop_of(asmc, rf"^_ZN6llampc10ctl_kernelILi{lpm}ELb0EEEvNS_9CtlLaunchE:", 300, 8))
+asmn = listing("nlp")
+# one Euler step (two divisions: the slip angles'), the staged fast run; the corridor instantiation
+# is the one with the NlpCorridor argument
+report("nlp Euler LPM 4 (staged, H <= 28)", loop_of(asmn, r"^_ZN6llampc10nlp_kernelILb1ELi512EJEEE\S+:", 60, 2, 100))
+report("nlp Euler LPM 4 (staged) + corridor", loop_of(asmn, r"^_ZN6llampc10nlp_kernelILb1ELi512EJNS_11NlpCorridorEEEE\S+:", 60, 2, 100))
+report("nlp Euler LPM 4 (unstaged, H > 28)", loop_of(asmn, r"^_ZN6llampc10nlp_kernelILb0ELi256EJEEE\S+:", 60, 2, 100))
+report("nlp Euler LPM 4 (unstaged) + corridor", loop_of(asmn, r"^_ZN6llampc10nlp_kernelILb0ELi256EJNS_11NlpCorridorEEEE\S+:", 60, 2, 100))
