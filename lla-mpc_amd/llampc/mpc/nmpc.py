@@ -17,6 +17,13 @@ mean and spread), the result comes back through pinned host memory.  Every retur
 ``umpc`` satisfies the NLP's bounds and rate constraints; ``fval`` is the objective of
 ``umpc`` and ``xmpc`` its Euler trajectory — the same triple IPOPT's feasible point would give.
 
+Rate bounds are symmetric on the device: ``params["min_rates"][j]`` = lo and ``["max_rates"][j]``
+= hi (both None: no bound on input j) are enforced as |u_k - u_{k-1}| <= m Ts with m = min(-lo, hi),
+by the rate chain and by the feasibility test alike.  An asymmetric pair is therefore solved on
+its tighter symmetric side (a subset of the NLP's feasible set): (-3, +5) rad/s gives the ±3
+rad/s solve.  (Until the chain and the test shared the bound, the chain clipped to [lo, hi] Ts and
+every sample it left beyond m Ts was scored +inf: the search all but stopped sampling.)
+
 A *corridor* keeps the search on the track: ``solve(x0, xref, uprev, corridor=hp)`` with ``hp``
 [H, 6], row k - 1 = (a0, a1, b, c0, c1, d) the half-planes a.p_k <= b and c.p_k <= d on the
 position p_k after k Euler steps (a = 0, b = +inf disables one).  Every sample's objective gains
@@ -70,13 +77,16 @@ class setupNLP:
         self.std_floor, self.seed, self.device = float(std_floor), int(seed), device
         self.umin = np.asarray(params["min_inputs"], dtype=np.float64)
         self.umax = np.asarray(params["max_inputs"], dtype=np.float64)
-        # steering-rate bounds min_rates[1]*Ts <= d delta <= max_rates[1]*Ts (nmpc.py:104-105);
-        # the pwm rate is unconstrained (None)
-        rmin = [None if r is None else float(r) * self.Ts for r in params["min_rates"]]
-        rmax = [None if r is None else float(r) * self.Ts for r in params["max_rates"]]
-        self.rate = list(zip(rmin, rmax))
-        # the kernel's feasibility test is symmetric |du| <= rate_max*Ts: use the tighter side
-        rate_max = tuple(-1.0 if lo is None else min(-lo, hi) / self.Ts for lo, hi in self.rate)
+        # rate bounds min_rates[j]*Ts <= d u_j <= max_rates[j]*Ts (nmpc.py:104-105: the steering
+        # rate; ORCA leaves the pwm rate None, unconstrained).  The kernel's feasibility test is
+        # symmetric, |du| <= rate_max*Ts: an asymmetric pair is narrowed to its tighter side
+        # m = min(-lo, hi), and the rate chain clips to the same [-m, +m]*Ts — every sample it
+        # produces is then feasible by construction (module doc).
+        rate_max = tuple(-1.0 if lo is None else min(-float(lo), float(hi))
+                         for lo, hi in zip(params["min_rates"], params["max_rates"]))
+        if any(lo is not None and not m >= 0 for m, lo in zip(rate_max, params["min_rates"])):
+            raise ValueError("min_rates must be <= 0 <= max_rates (the symmetric rate bound min(-lo, hi))")
+        self.rate = [(None, None) if m < 0 else (-m * self.Ts, m * self.Ts) for m in rate_max]
         self.cost = nat.cost_struct(Q=Q, R=R, P=P, umin=self.umin, umax=self.umax,
                                     rate_max=rate_max, enforce_bounds=True)
         self._bank = None
