@@ -39,6 +39,10 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
                           __builtin_amdgcn_readlane(__double2loint(v), l));
 }
+__device__ __forceinline__ double readfirstlane_d(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                          __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
 __device__ __forceinline__ int64_t readlane_l(int64_t v, int l) {
   const uint64_t u = (uint64_t)v;
   const uint64_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, l);
@@ -189,6 +193,57 @@ __device__ __forceinline__ int wave_sum(int x) {
 // constants; left in SGPRs they overflow the 102-SGPR budget together with the
 // polynomial constants and get spilled to VGPR lanes (v_readlane reloads in the loop).
 __device__ __forceinline__ void pin_vgpr(double& x) { asm volatile("" : "+v"(x)); }
+
+// The plan kernels' first instructions: one scalar load from every 64-byte line of the
+// explicit kernel arguments, all in flight together, then one wait.  The scalar cache is cold
+// at every launch and the compiler reads the arguments where it needs them, in groups that
+// each wait for their own miss (the look-ahead path: four groups in series before its first
+// input load); after this touch those reads hit.  BYTES: the arguments' size.  The segment's
+// base is only 8-byte aligned, so the arguments span kArgLines lines or one more: the extra
+// load reads the last argument word.  The loads and their wait are one statement and the
+// dummy destinations early-clobber, so no destination is reused while its load is in flight.
+// Returns the segment's base as the statement's own output: argument loads are invariant, so
+// the compiler places those of the by-value parameters above any statement of the kernel;
+// the kernels read their arguments through this pointer instead (kernarg_at), plain scalar
+// loads as before, which therefore follow the touch.
+typedef const __attribute__((address_space(4))) unsigned char* KernargPtr;
+constexpr int kArgLines = 15;
+template <int BYTES>
+__device__ __forceinline__ KernargPtr touch_kernargs() {
+  static_assert((BYTES + 63) / 64 == kArgLines, "touch_kernargs: one load per line of the arguments");
+  constexpr int kLast = BYTES - 4;
+  static_assert(kLast >= 64 * (kArgLines - 1) && kLast % 4 == 0, "the last word lies in the last line");
+  uint64_t base = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+  uint32_t d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15;
+  asm volatile(
+      "s_load_dword %0, %16, 0x0\n\t"
+      "s_load_dword %1, %16, 0x40\n\t"
+      "s_load_dword %2, %16, 0x80\n\t"
+      "s_load_dword %3, %16, 0xc0\n\t"
+      "s_load_dword %4, %16, 0x100\n\t"
+      "s_load_dword %5, %16, 0x140\n\t"
+      "s_load_dword %6, %16, 0x180\n\t"
+      "s_load_dword %7, %16, 0x1c0\n\t"
+      "s_load_dword %8, %16, 0x200\n\t"
+      "s_load_dword %9, %16, 0x240\n\t"
+      "s_load_dword %10, %16, 0x280\n\t"
+      "s_load_dword %11, %16, 0x2c0\n\t"
+      "s_load_dword %12, %16, 0x300\n\t"
+      "s_load_dword %13, %16, 0x340\n\t"
+      "s_load_dword %14, %16, 0x380\n\t"
+      "s_load_dword %15, %16, %17\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&s"(d0), "=&s"(d1), "=&s"(d2), "=&s"(d3), "=&s"(d4), "=&s"(d5), "=&s"(d6), "=&s"(d7), "=&s"(d8),
+        "=&s"(d9), "=&s"(d10), "=&s"(d11), "=&s"(d12), "=&s"(d13), "=&s"(d14), "=&s"(d15), "+s"(base)
+      : "i"(kLast)
+      : "memory");
+  return (KernargPtr)base;
+}
+// The argument of type T at byte offset `off` of the segment.
+template <typename T>
+__device__ __forceinline__ const T& kernarg_at(KernargPtr p, int off) {
+  return *(const T*)reinterpret_cast<const __attribute__((address_space(4))) T*>(p + off);
+}
 
 }  // namespace
 

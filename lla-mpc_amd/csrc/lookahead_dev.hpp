@@ -87,9 +87,15 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
   const int soff = (XM && mpb < kBlock) ? mpb : 0;
   Tire t{};
   if (!WQ && live) t = load_tire(a.params, a.n, n);
+  // kBatch: the shared-xref prologue that issues every input load in one batch (below).  The
+  // raceline reference and the work-queue layout keep the plain prologue (the work-queue tick
+  // measured 0.7 % slower with the batch and the argument touch, 358.8 -> 361.4 us at C = 64).
+  constexpr bool kBatch = !XM && !WQ;
   double x0[6];
+  if constexpr (!kBatch) {
 #pragma unroll
-  for (int m = 0; m < 6; ++m) x0[m] = a.x0[m];
+    for (int m = 0; m < 6; ++m) x0[m] = a.x0[m];
+  }
   // XM = 1 (per-model raceline reference): knots [n] and the x/y spline rows [2][4][n-1]
   // after the (optional) U staging; a.xref holds the shared start {s0, v0, scale}
   double* rl_knots = su + (STAGE ? kStageW * C * H : 0);
@@ -190,84 +196,186 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
     RL_STAMP(blk, 2);
     __threadfence_block();
     RL_STAMP(blk, 3);
-  } else {
+  } else if (!kBatch) {
     for (int e = threadIdx.x; e <= H; e += BT) {
       sx[2 * e] = a.xref[e];
       sx[2 * e + 1] = a.xref[(H + 1) + e];
     }
   }
+  // One staged record [k][c] -> (pwm, delta, sin delta, cos delta): the steering's sincos depends
+  // only on the shared candidates, so it is formed once per block (same evaluation as
+  // make_input_fast: the fast core on its domain, the general function off it).  RK4 stages
+  // the fused stages' input terms instead: (F0, F1, h/m sin d, h/m cos d, h lf/Iz cos d,
+  // delta) — dyn.hpp fused_in, with the shared constants of make_fused.  (ua, dl): the
+  // candidate's input at step k, (p0, p1): the input before it.
+  auto stage_write = [&](int c, int k, double ua, double dl, double sd, double cd, double p0, double p1,
+                         const FusedK& fq0) {
+    double* o = su + kStageW * (k * C + c);
+    const double d0 = ua - p0, d1 = dl - p1;
+    if (INTEG == 0) {
+      const FusedIn fi = fused_in(fq0, Input{ua, dl, sd, cd});
+      o[0] = fi.F0;
+      o[1] = fi.F1;
+      o[2] = fi.hmsd;
+      o[3] = fi.hmcd;
+      o[4] = fi.c5a;
+      o[5] = dl;
+    } else {
+      o[0] = ua;
+      o[1] = dl;
+      o[2] = sd;
+      o[3] = cd;
+    }
+    o[6] = act_term(a.cost, d0, d1);
+    o[7] = (!a.cost.enforce || input_feasible(a.cost, ua, dl, d0, d1)) ? 1.0 : 0.0;
+  };
+  // the rollouts' uniform constants in VGPRs (pin_vgpr, dev_wave.hpp)
+  CostK q = a.cost;
+  VehK veh = a.veh;
+  double Ts = a.Ts;
+  auto pin_consts = [&] {
+    for (int m = 0; m < 4; ++m) {
+      pin_vgpr(q.Q[m]);
+      pin_vgpr(q.R[m]);
+      pin_vgpr(q.P[m]);
+    }
+    for (int m = 0; m < 2; ++m) {
+      pin_vgpr(q.umin[m]);
+      pin_vgpr(q.umax[m]);
+      pin_vgpr(q.dmax[m]);
+    }
+    pin_vgpr(veh.lf);
+    pin_vgpr(veh.lr);
+    pin_vgpr(veh.mass);
+    pin_vgpr(veh.inv_mass);
+    pin_vgpr(veh.inv_Iz);
+    pin_vgpr(veh.Cm1);
+    pin_vgpr(veh.Cm2);
+    pin_vgpr(veh.Cr0);
+    pin_vgpr(veh.Cr2);
+    pin_vgpr(Ts);
+  };
+  // this lane's model: the stage constants of its Pacejka row.  LPM = 2: lane 0 of the pair
+  // evaluates the front chain, lane 1 the rear (dyn.hpp); fused RK4 quads carry W = h omega
+  // and Psi = (2/pi) psi (make_fused): the chains' lw / h turns W back into omega
+  constexpr bool kScaled = (INTEG == 0 && scaled_yaw(LPM));
+  StageK sk;
+  FusedK fq;
+  auto model_setup = [&] {
+    sk = make_stage<LPM>(veh, t, sub, INTEG == 0 ? Ts : 1.0);
+    if (kScaled) sk.ch[0].lw = sk.ch[0].lw / Ts;
+    if (kScaled && LPM == 1) sk.ch[1].lw = sk.ch[1].lw / Ts;
+    if (kScaled && LPM == 4 && sub >= 2) {
+      // lanes 2/3 run their (discarded) chain on zero operands — yy = z = 0, no extra
+      // instruction: fewer toggling bits, a higher clock (A/B 28.86 -> 28.61 us/tick).
+      // (Freezing the unused yaw of lanes 0/1 as well, by per-lane RK4 weights 0: 28.98.)
+      sk.ch[0].lw = 0.0;
+      sk.ch[0].sg = 0.0;
+      sk.ch[0].B = 0.0;
+      sk.ch[0].nsB = 0.0;
+    }
+    fq = make_fused(veh, sk, Ts, kScaled);
+  };
   // Shared xref: ONE FmK for the staging below and the rollouts (the staging uses its sincos
   // constants, the same in the lean and precise sets) instead of materialising the ~50
   // constants twice on the prologue's critical path; the raceline variant keeps two loads
   // (holding them across its prologue spilled, round 1).
   fm::FmK K0;
-  if constexpr (!XM) K0 = fm::FmK::load<kLeanLA && INTEG == 0>();
-  if (STAGE) {
-    // [k][c] -> (pwm, delta, sin delta, cos delta): the steering's sincos depends only on the
-    // shared candidates, so it is formed once per block here (same evaluation as
-    // make_input_fast: the fast core on its domain, the general function off it).  RK4
-    // stages the fused stages' input terms instead: (F0, F1, h/m sin d, h/m cos d,
-    // h lf/Iz cos d, delta) — dyn.hpp fused_in, with the shared constants of make_fused.
-    const fm::FmK K = [&] {
-      if constexpr (XM) return fm::FmK::load();
-      else return K0;
-    }();
-    const FusedK fq0 = make_fused(a.veh, make_stage<1>(a.veh, Tire{}, 0), a.Ts, scaled_yaw(LPM));
-    for (int e = (int)threadIdx.x - soff; e < C * H; e += BT - soff) {
-      if (e < 0) break;
-      const int c = e / H, k = e - c * H;
-      const double dl = a.U[2 * e + 1];
-      double sd, cd;
-      if (fm::sincos_fast_ok(dl)) fm::sincos_fast(dl, &sd, &cd, K);
-      else LL_SINCOS(dl, &sd, &cd);
-      double* o = su + kStageW * (k * C + c);
-      const double ua = a.U[2 * e];
-      const double p0 = k ? a.U[2 * e - 2] : a.uprev[0], p1 = k ? a.U[2 * e - 1] : a.uprev[1];
-      const double d0 = ua - p0, d1 = dl - p1;
-      if (INTEG == 0) {
-        const FusedIn fi = fused_in(fq0, Input{ua, dl, sd, cd});
-        o[0] = fi.F0;
-        o[1] = fi.F1;
-        o[2] = fi.hmsd;
-        o[3] = fi.hmcd;
-        o[4] = fi.c5a;
-        o[5] = dl;
-      } else {
-        o[0] = ua;
-        o[1] = dl;
-        o[2] = sd;
-        o[3] = cd;
+  double up0, up1;
+  if constexpr (!kBatch) {
+    if constexpr (!XM) K0 = fm::FmK::load<kLeanLA && INTEG == 0>();
+    if (STAGE) {
+      const fm::FmK K = [&] {
+        if constexpr (XM) return fm::FmK::load();
+        else return K0;
+      }();
+      const FusedK fq0 = make_fused(a.veh, make_stage<1>(a.veh, Tire{}, 0), a.Ts, scaled_yaw(LPM));
+      for (int e = (int)threadIdx.x - soff; e < C * H; e += BT - soff) {
+        if (e < 0) break;
+        const int c = e / H, k = e - c * H;
+        const double dl = a.U[2 * e + 1];
+        double sd, cd;
+        if (fm::sincos_fast_ok(dl)) fm::sincos_fast(dl, &sd, &cd, K);
+        else LL_SINCOS(dl, &sd, &cd);
+        const double ua = a.U[2 * e];
+        const double p0 = k ? a.U[2 * e - 2] : a.uprev[0], p1 = k ? a.U[2 * e - 1] : a.uprev[1];
+        stage_write(c, k, ua, dl, sd, cd, p0, p1, fq0);
       }
-      o[6] = act_term(a.cost, d0, d1);
-      o[7] = (!a.cost.enforce || input_feasible(a.cost, ua, dl, d0, d1)) ? 1.0 : 0.0;
     }
+    __syncthreads();
+    pin_consts();
+    up0 = a.uprev[0];
+    up1 = a.uprev[1];
+  } else {
+    // Shared xref, a block per models: every input of the prologue in ONE memory round trip.  Behind the row loads
+    // each thread issues the start state, the previous input, its reference element and its
+    // staging element's inputs (the step's and the one before it) before anything waits for
+    // any of them; the per-model setup runs under that latency, then the LDS writes and the
+    // sincos from registers.  Indices are clamped and the loads unconditional (as copy_lds:
+    // no load leaves its array, the surplus ones are not used).  The block-uniform start
+    // state and previous input are loaded per lane through an opaque zero offset, so they are
+    // vector loads counted in order with the others (a scalar load would be waited for at
+    // once: its registers spill to lanes), and made uniform again by readfirstlane.
+    const int CH = C * H, tid = (int)threadIdx.x;
+    uint32_t zoff;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zoff));
+    const double* gx0 = a.x0 + zoff;
+    const double* gup = a.uprev + zoff;
+    double xv[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) xv[m] = gx0[m];
+    const double uv0 = gup[0], uv1 = gup[1];
+    const int ex = tid < H ? tid : H;
+    const double xr0 = a.xref[ex], xr1 = a.xref[(H + 1) + ex];
+    // a staging element's loads: its input pair and the pair before it (element e - 1; at a
+    // candidate's first step the previous input instead, chosen in stage_elem)
+    auto stage_load = [&](int e, double& ua, double& dl, double& p0, double& p1) {
+      const int ec = e < CH ? e : CH - 1, ep = ec > 0 ? ec - 1 : 0;
+      ua = a.U[2 * ec];
+      dl = a.U[2 * ec + 1];
+      p0 = a.U[2 * ep];
+      p1 = a.U[2 * ep + 1];
+    };
+    double sua = 0.0, sdl = 0.0, sp0 = 0.0, sp1 = 0.0;
+    if (STAGE) stage_load(tid, sua, sdl, sp0, sp1);
+    // under the loads' latency: the polynomial constants, the pins, this lane's model
+    K0 = fm::FmK::load<kLeanLA && INTEG == 0>();
+    pin_consts();
+    model_setup();
+    for (int e = tid; e <= H; e += BT) {               // one pass unless H >= BT
+      sx[2 * e] = e == tid ? xr0 : a.xref[e];
+      sx[2 * e + 1] = e == tid ? xr1 : a.xref[(H + 1) + e];
+    }
+#pragma unroll
+    for (int m = 0; m < 6; ++m) x0[m] = readfirstlane_d(xv[m]);
+    up0 = readfirstlane_d(uv0);
+    up1 = readfirstlane_d(uv1);
+    if (STAGE) {
+      const FusedK fq0 = make_fused(a.veh, make_stage<1>(a.veh, Tire{}, 0), a.Ts, scaled_yaw(LPM));
+      auto stage_elem = [&](int e, double ua, double dl, double p0, double p1) {
+        const int c = C == 1 ? 0 : e / H, k = e - c * H;     // C == 1: launch-uniform, no division
+        double sd, cd;
+        if (fm::sincos_fast_ok(dl)) fm::sincos_fast(dl, &sd, &cd, K0);
+        else LL_SINCOS(dl, &sd, &cd);
+        stage_write(c, k, ua, dl, sd, cd, k ? p0 : uv0, k ? p1 : uv1, fq0);
+      };
+      if (tid < CH) stage_elem(tid, sua, sdl, sp0, sp1);
+      // C H above the block: kStageBatch elements per thread and pass, their loads together
+      constexpr int kStageBatch = 4;
+      for (int base = tid + BT; base < CH; base += kStageBatch * BT) {
+        double ua[kStageBatch], dl[kStageBatch], p0[kStageBatch], p1[kStageBatch];
+#pragma unroll
+        for (int j = 0; j < kStageBatch; ++j) stage_load(base + j * BT, ua[j], dl[j], p0[j], p1[j]);
+#pragma unroll
+        for (int j = 0; j < kStageBatch; ++j)
+          if (base + j * BT < CH) stage_elem(base + j * BT, ua[j], dl[j], p0[j], p1[j]);
+      }
+    }
+    // a lane past the reference's or the staging's end never reads its clamped loads: without
+    // this use the wait for them lands in the rollout loop, where their registers are reused
+    asm volatile("" ::"v"(xr0), "v"(xr1), "v"(sua), "v"(sdl), "v"(sp0), "v"(sp1));
+    __syncthreads();
   }
-  __syncthreads();
-
-  CostK q = a.cost;
-  VehK veh = a.veh;
-  double Ts = a.Ts;
-  for (int m = 0; m < 4; ++m) {
-    pin_vgpr(q.Q[m]);
-    pin_vgpr(q.R[m]);
-    pin_vgpr(q.P[m]);
-  }
-  for (int m = 0; m < 2; ++m) {
-    pin_vgpr(q.umin[m]);
-    pin_vgpr(q.umax[m]);
-    pin_vgpr(q.dmax[m]);
-  }
-  pin_vgpr(veh.lf);
-  pin_vgpr(veh.lr);
-  pin_vgpr(veh.mass);
-  pin_vgpr(veh.inv_mass);
-  pin_vgpr(veh.inv_Iz);
-  pin_vgpr(veh.Cm1);
-  pin_vgpr(veh.Cm2);
-  pin_vgpr(veh.Cr0);
-  pin_vgpr(veh.Cr2);
-  pin_vgpr(Ts);
-  const double up0 = a.uprev[0], up1 = a.uprev[1];
 
   double bv = __builtin_nan("");
   int64_t bc = kNoIndex;
@@ -398,23 +506,7 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
     return;
   }
   if (live) {
-    // LPM = 2: lane 0 of the pair evaluates the front chain, lane 1 the rear (dyn.hpp)
-    // fused RK4 quads carry W = h omega and Psi = (2/pi) psi (make_fused): the chains'
-    // lw / h turns W back into omega
-    constexpr bool kScaled = (INTEG == 0 && scaled_yaw(LPM));
-    StageK sk = make_stage<LPM>(veh, t, sub, INTEG == 0 ? Ts : 1.0);
-    if (kScaled) sk.ch[0].lw = sk.ch[0].lw / Ts;
-    if (kScaled && LPM == 1) sk.ch[1].lw = sk.ch[1].lw / Ts;
-    if (kScaled && LPM == 4 && sub >= 2) {
-      // lanes 2/3 run their (discarded) chain on zero operands — yy = z = 0, no extra
-      // instruction: fewer toggling bits, a higher clock (A/B 28.86 -> 28.61 us/tick).
-      // (Freezing the unused yaw of lanes 0/1 as well, by per-lane RK4 weights 0: 28.98.)
-      sk.ch[0].lw = 0.0;
-      sk.ch[0].sg = 0.0;
-      sk.ch[0].B = 0.0;
-      sk.ch[0].nsB = 0.0;
-    }
-    const FusedK fq = make_fused(veh, sk, Ts, kScaled);
+    if constexpr (!kBatch) model_setup();   // the batched prologue: ahead of the barrier
     const fm::FmK K = [&] {
       if constexpr (XM) return fm::FmK::load<kLeanLA && INTEG == 0>();
       else return K0;

@@ -63,20 +63,41 @@ __device__ __forceinline__ void plan_body(const LookbackLaunch& lb, const Lookah
   if constexpr (PX) peer_finish(fin, smem);
 }
 
+// The plan kernels' arguments ahead of the inline pack: three launch structs and (G, cpl), each
+// a multiple of its successor's alignment, so they lie back to back from the segment's start.
+constexpr int kArgLa = sizeof(LookbackLaunch), kArgFin = kArgLa + sizeof(LookaheadLaunch);
+constexpr int kArgG = kArgFin + sizeof(FinalLaunch), kPlanArgBytes = kArgG + 2 * sizeof(int);
+static_assert(sizeof(LookbackLaunch) % 8 == 0 && sizeof(LookaheadLaunch) % 8 == 0 && sizeof(FinalLaunch) % 8 == 0,
+              "plan kernel arguments: no padding between the launch structs");
+
 // PX: the sharded tick's fused peer exchange (a separate instantiation, so the plain tick's
 // code is unchanged: inlining it into every variant cost the headline tick 0.5 us)
+// The shared-xref variants read their arguments behind touch_kernargs (dev_wave.hpp), through
+// the pointer it returns; the by-value parameters only give the segment its layout.  The
+// raceline variants keep the by-value reads (the touch ahead of those cost their unstaged
+// instantiation 36 bytes of scratch per lane), and so does the work-queue layout (its tick
+// was slower with the touch and the batched prologue, lookahead_dev.hpp kBatch).
 template <int INTEG, bool STAGE, int LPM, int XM, bool PX = false, int WQ = 0>
 __global__ __launch_bounds__(wq_threads(WQ)) void plan_kernel(LookbackLaunch lb, LookaheadLaunch la,
                                                       FinalLaunch fin, int G, int cpl) {
-  plan_body<INTEG, STAGE, LPM, XM, PX, WQ>(lb, la, fin, G, cpl);
+  if constexpr (XM || WQ) {
+    plan_body<INTEG, STAGE, LPM, XM, PX, WQ>(lb, la, fin, G, cpl);
+  } else {
+    const KernargPtr kp = touch_kernargs<kPlanArgBytes>();
+    plan_body<INTEG, STAGE, LPM, XM, PX, WQ>(kernarg_at<LookbackLaunch>(kp, 0), kernarg_at<LookaheadLaunch>(kp, kArgLa),
+                                             kernarg_at<FinalLaunch>(kp, kArgFin), kernarg_at<int>(kp, kArgG),
+                                             kernarg_at<int>(kp, kArgG + 4));
+  }
 }
 
 // The same tick with its inputs in the kernarg segment (InlinePack): the pointers are set to
 // the pack's fields, read by flat loads like any other input (no H2D copy on the host path).
 template <int LPM>
-__global__ __launch_bounds__(kBlock) void plan_kernel_inl(LookbackLaunch lb, LookaheadLaunch la,
-                                                          FinalLaunch fin, int G, int cpl,
+__global__ __launch_bounds__(kBlock) void plan_kernel_inl(LookbackLaunch, LookaheadLaunch, FinalLaunch, int, int,
                                                           InlinePack pk) {
+  const KernargPtr kp = touch_kernargs<kPlanArgBytes>();   // the pack is not touched: flat loads
+  LookbackLaunch lb = kernarg_at<LookbackLaunch>(kp, 0);
+  LookaheadLaunch la = kernarg_at<LookaheadLaunch>(kp, kArgLa);
   const double* v = pk.v;
   lb.x_prev = v;
   lb.u_prev = v + 6;
@@ -85,7 +106,8 @@ __global__ __launch_bounds__(kBlock) void plan_kernel_inl(LookbackLaunch lb, Loo
   la.uprev = v + 14;
   la.xref = v + 16;
   la.U = v + 16 + 2 * (la.H + 1);
-  plan_body<0, true, LPM, 0>(lb, la, fin, G, cpl);
+  plan_body<0, true, LPM, 0>(lb, la, kernarg_at<FinalLaunch>(kp, kArgFin), kernarg_at<int>(kp, kArgG),
+                             kernarg_at<int>(kp, kArgG + 4));
 }
 
 constexpr size_t kOneBlockPerCuLds = 82 * 1024;

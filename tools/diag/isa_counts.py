@@ -25,7 +25,9 @@ def listing(tu):
 
 def loop_of(asm, pattern, fmin=150, rcp=1, nmin=200):
     s = next(i for i, l in enumerate(asm) if re.match(pattern, l))
-    e = next(i for i in range(s, len(asm)) if "s_endpgm" in asm[i])
+    # the kernel's end, not its first s_endpgm: a block that ends the program may be laid out
+    # ahead of the loop
+    e = next(i for i in range(s, len(asm)) if re.match(r"^\.Lfunc_end\d+:", asm[i]))
     body = asm[s:e]
     labels = {m.group(1): i for i, l in enumerate(body) if (m := re.match(r"^(\.LBB\d+_\d+):", l))}
     best = None
