@@ -233,6 +233,12 @@ constexpr int kQuadX1 = 0xB1, kQuadX2 = 0x4E;
 // Position split (LPM = 4): lanes with pc = 0 (0, 2) carry X, pc = 1 (1, 3) carry Y.  A =
 // [3,2,3,2] (X lanes get h cos psi, Y lanes h sin psi), B = [2,3,2,3] (the other one).
 constexpr int kQuadPosA = 0xBB, kQuadPosB = 0xEE;
+// How a fused LPM-4 rollout carries the position (the POS argument of forces_fast, k_fused and
+// step_fused).  kPosBoth: X and Y in every lane.  kPosSplit: one component per lane, h sin psi
+// and h cos psi broadcast to it every stage (above).  kPosQuadr: one component per lane 2 / 3,
+// built once per step from RK4-weighted sums that every lane forms of its OWN chain result —
+// no position broadcast in the stage (step_fused).
+constexpr int kPosBoth = 0, kPosSplit = 1, kPosQuadr = 2;
 
 // One tire's constants in this lane: front (lw = lf, sg = +1) or rear (lw = lr, sg = -1).
 struct Chain {
@@ -417,9 +423,10 @@ struct StageF {
   double Ffy, Fry, sp, cp;
 };
 // Bd = B d fw, the chain's steering term (LPM = 4 only; formed once per step).
-// SPLIT (LPM = 4, position split): sp/cp carry the split's A/B operands instead (X lanes:
-// cos, sin; Y lanes: sin, cos — kQuadPosA/B).
-template <int LPM, bool SPLIT = false, bool SCALED = false, bool LEAN = false>
+// POS (LPM = 4): kPosSplit — sp/cp carry the split's A/B operands instead (X lanes: cos, sin;
+// Y lanes: sin, cos — kQuadPosA/B); kPosQuadr — sp is the lane's own chain result (lanes 0/1
+// their force, lane 2 h sin psi, lane 3 h cos psi), cp is unused: two broadcasts, not four.
+template <int LPM, int POS = kPosBoth, bool SCALED = false, bool LEAN = false>
 __device__ __forceinline__ StageF forces_fast(const StageK& sk, double den, double vy, double om,
                                               double d, double psi, const fm::FmK& K, Dom& dm,
                                               double Bd = 0.0) {
@@ -429,7 +436,10 @@ __device__ __forceinline__ StageF forces_fast(const StageK& sk, double den, doub
     const double r = chain_fold<SCALED, LEAN>(sk.ch[0], den, vy, om, Bd, psi, sk.ra, sk.pm, sk.po, dm, K);
     f.Ffy = quad_bcast<kQuad0, 0>(r);
     f.Fry = quad_bcast<kQuad1, 1>(r);
-    if constexpr (SPLIT) {
+    if constexpr (POS == kPosQuadr) {
+      f.sp = r;
+      f.cp = 0.0;
+    } else if constexpr (POS == kPosSplit) {
       f.sp = quad_bcast<kQuadPosA, 2>(r);
       f.cp = quad_bcast<kQuadPosB, 3>(r);
     } else {
@@ -516,7 +526,9 @@ __device__ __forceinline__ Input make_input_fast(double a, double d, const fm::F
 // FmK::load<kLeanLA>()): ~1e-13 relative on the tire forces (8 terms, round 4; ~1e-14 with 9);
 // 456 instructions per step at LPM 4 (467 with 9 terms, 494 with the precise 10-term cores,
 // 507 in round 2), A/B 28.8 -> 27.2 us per tick with 9 terms (profiles/r03/ab_lean), 26.6
-// with 8 (profiles/r04/ab_lean8.log).
+// with 8 (profiles/r04/ab_lean8.log).  The plan kernel's staged quad loop is 461 instructions
+// per step with the position split and 440 with the position quadrature (step_fused
+// kPosQuadr, round 8: -4 fp64, -14 DPP moves, -3 s_nop).
 constexpr bool kLeanLA = true;
 
 struct FusedK {
@@ -554,22 +566,28 @@ __device__ __forceinline__ FusedK make_fused(const VehK& v, const StageK& sk, do
   return q;
 }
 
-// SPLIT (LPM = 4 only): the quad's lanes integrate ONE position component each — X on pc =
-// 0, Y on pc = 1 — in k[0]/x[0] (k[1]/x[1] unused): the position feeds nothing but the cost,
-// so the component's increment, stage sums and tracking term are formed once instead of
+// POS = kPosSplit (LPM = 4 only): the quad's lanes integrate ONE position component each — X
+// on pc = 0, Y on pc = 1 — in k[0]/x[0] (k[1]/x[1] unused): the position feeds nothing but the
+// cost, so the component's increment, stage sums and tracking term are formed once instead of
 // twice in every lane.  X: vx hcos - vy hsin; Y: vx hsin + vy hcos = fma(vx, A, psg vy B).
-template <int LPM, bool SPLIT = false>
+// POS = kPosQuadr: no position increment here at all — k[0] returns the lane's own chain
+// result r and step_fused sums vy r and vx r over the stages (the position is a quadrature of
+// what the lanes already hold: it feeds no stage).
+template <int LPM, int POS = kPosBoth>
 __device__ __forceinline__ void k_fused(const StageK& sk, const FusedK& q, double F0, double F1,
                                         double hmsd, double hmcd, double c5a, double d, double Bd,
                                         const double* y, double* k, const fm::FmK& K, Dom& dm) {
   const double vx = y[3], vy = y[4], om = y[5];
   constexpr bool kScaled = scaled_yaw(LPM);   // om = W = h omega, y[2] = Psi (make_fused)
-  const StageF f = forces_fast<LPM, SPLIT, kScaled, kLeanLA>(sk, vx, vy, om, d, y[2], K, dm, Bd);
+  const StageF f = forces_fast<LPM, POS, kScaled, kLeanLA>(sk, vx, vy, om, d, y[2], K, dm, Bd);
   // h sin(psi), h cos(psi): LPM = 4 lanes 2/3 scale their sine by h already (make_stage)
   const double hsp = (LPM == 4) ? f.sp : q.h * f.sp, hcp = (LPM == 4) ? f.cp : q.h * f.cp;
   const double hmFrx = fma(vx, fma(q.m3, vx, F1), F0);                     // hm Frx
   k[2] = kScaled ? om : q.h * om;
-  if constexpr (SPLIT) {
+  if constexpr (POS == kPosQuadr) {
+    k[0] = f.sp;                                                          // r (step_fused)
+    k[1] = 0.0;
+  } else if constexpr (POS == kPosSplit) {
     k[0] = fma(vx, hsp, (sk.psg * vy) * hcp);                             // (A, B) in (sp, cp)
     k[1] = 0.0;
   } else {
@@ -590,53 +608,84 @@ __device__ __forceinline__ FusedIn fused_in(const FusedK& q, const Input& u) {
   return FusedIn{fma(q.m1, u.a, -q.m0), -(q.m2 * u.a), q.hm * u.sd, q.hm * u.cd, q.hIlf * u.cd};
 }
 
-template <int LPM, bool SPLIT = false>
+// POS = kPosQuadr (the plan kernel's quads, diagonal Q and P): with r the lane's own chain
+// result of a stage (lane 2: h sin psi, lane 3: h cos psi), every lane sums P = sum w vy r and
+// G = sum w vx r with the RK4 weights w = 1, 2, 2, 1 by accumulation — stages 1 and 4 into
+// (P, G), 2 and 3 into (Pm, Gm), then P += 2 Pm, G += 2 Gm: 2 instructions per stage and 2
+// more.  Once per step ONE xor-1 swap of G, and the lane's component increment is
+// fma(psg, P, G') : lane 2 (psg = -1) X = G_3 - P_2 = sum w (vx h cos - vy h sin), lane 3
+// (psg = +1) Y = G_2 + P_3 — 12 fp64 instructions and 2 DPP moves per step where kPosSplit has
+// 16 and 16.  The valid position is in lanes 2/3 (pc = 0 / 1 as on lanes 0/1); lanes 0/1 sum
+// their forces times the velocities into x[0]: finite or not, the caller must not use it
+// (rollout_dev.hpp takes the tracking terms of lanes 2 and 3 only).  The sums' order differs
+// from kPosSplit's per-stage increments: ~1 ulp per step on the positions; velocities, yaw
+// and the domain record are the same instructions on the same operands.
+template <int LPM, int POS = kPosBoth>
 __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, double* x,
                                            const FusedIn& fi, double ud, const fm::FmK& K,
                                            Dom& dm) {
-  static_assert(!SPLIT || LPM == 4, "the position split needs the quad");
+  static_assert(POS == kPosBoth || LPM == 4, "the position split needs the quad");
+  constexpr bool SPLIT = POS != kPosBoth, QUADR = POS == kPosQuadr;
   const double F0 = fi.F0, F1 = fi.F1, hmsd = fi.hmsd, hmcd = fi.hmcd, c5a = fi.c5a;
   const Input u{0.0, ud, 0.0, 0.0};                       // k_fused reads u.d only
   const double Bd = (LPM == 4) ? sk.ch[0].B * (u.d * sk.fw) : 0.0;
   double y[6], k[6], acc[6];
   y[1] = acc[1] = 0.0;
-  k_fused<LPM, SPLIT>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, x, k, K, dm);
+  [[maybe_unused]] double P = 0.0, G = 0.0, Pm = 0.0, Gm = 0.0;            // QUADR: the stage sums
+  k_fused<LPM, POS>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, x, k, K, dm);
+  if constexpr (QUADR) {
+    P = x[4] * k[0];
+    G = x[3] * k[0];
+  }
   // the quad's yaw is Psi = (2/pi) psi with increment W (make_fused): weights x 2/pi
   constexpr bool kScaled = scaled_yaw(LPM);
   const double c2 = kScaled ? K.inv_pi : 0.5, c4 = kScaled ? K.two_pi : 1.0,
                c6 = kScaled ? K.inv_3pi : K.sixth;
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    if (SPLIT && i == 1) continue;
+    if ((SPLIT && i == 1) || (QUADR && i == 0)) continue;
     acc[i] = k[i];
     y[i] = fma(i == 2 ? c2 : 0.5, k[i], x[i]);
   }
-  k_fused<LPM, SPLIT>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  k_fused<LPM, POS>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  if constexpr (QUADR) {
+    Pm = y[4] * k[0];
+    Gm = y[3] * k[0];
+  }
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    if (SPLIT && i == 1) continue;
+    if ((SPLIT && i == 1) || (QUADR && i == 0)) continue;
     acc[i] = fma(2.0, k[i], acc[i]);
     y[i] = fma(i == 2 ? c2 : 0.5, k[i], x[i]);
   }
-  k_fused<LPM, SPLIT>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  k_fused<LPM, POS>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  if constexpr (QUADR) {
+    Pm = fma(y[4], k[0], Pm);
+    Gm = fma(y[3], k[0], Gm);
+  }
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    if (SPLIT && i == 1) continue;
+    if ((SPLIT && i == 1) || (QUADR && i == 0)) continue;
     acc[i] = fma(2.0, k[i], acc[i]);
     y[i] = (i == 2 && kScaled) ? fma(c4, k[i], x[i]) : x[i] + k[i];
   }
-  k_fused<LPM, SPLIT>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  k_fused<LPM, POS>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  if constexpr (QUADR) {
+    P = fma(2.0, Pm, fma(y[4], k[0], P));
+    G = fma(2.0, Gm, fma(y[3], k[0], G));
+    x[0] = fma(fma(sk.psg, P, dpp_bcast<kQuadX1>(G)), K.sixth, x[0]);
+  }
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    if (SPLIT && i == 1) continue;
+    if ((SPLIT && i == 1) || (QUADR && i == 0)) continue;
     x[i] = fma(acc[i] + k[i], i == 2 ? c6 : K.sixth, x[i]);
   }
 }
 
-template <int LPM, bool SPLIT = false>
+template <int LPM, int POS = kPosBoth>
 __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, double* x,
                                            const Input& u, const fm::FmK& K, Dom& dm) {
-  step_fused<LPM, SPLIT>(sk, q, x, fused_in(q, u), u.d, K, dm);
+  step_fused<LPM, POS>(sk, q, x, fused_in(q, u), u.d, K, dm);
 }
 
 // One look-ahead step on the fast path.

@@ -387,7 +387,8 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
   constexpr bool kSplit = (INTEG == 0 && LPM == 4);
   // the rollouts' variant: the re-run of bad lanes is kRF itself, the fast run adds kRFast
   constexpr unsigned kRF = (STAGE ? kRStage : 0u) | (XM ? kRXm : 0u);
-  constexpr unsigned kRSplitQ = kSplit ? kRSplit : 0u;      // the quad's position split
+  // the quad's position split, as a per-step quadrature in lanes 2/3 (dyn.hpp step_fused kPosQuadr)
+  constexpr unsigned kRSplitQ = kSplit ? (kRSplit | kRQuadr) : 0u;
   const bool diagQP = a.cost.Q[1] == 0.0 && a.cost.Q[2] == 0.0 && a.cost.P[1] == 0.0 && a.cost.P[2] == 0.0;
   if constexpr (WQ) {
     static_assert(LPM == 1 && XM == 0, "work queue: LPM 1, shared xref");

@@ -70,6 +70,9 @@ enum RolloutFlag : unsigned {
   kRDefer = 1u << 7,  // DEFER (ctl.hip ctl_spec, with SPLIT and S4): positions to `dpos`, the rest to *dout
   kRCorr = 1u << 8,   // CORR (nlp.hip's corridor solve): two position half-planes per step at `hp` [H][6] (LDS), the
                       //   squared slacks summed over the horizon, J + cw pen (corridor_slack2 below)
+  kRQuadr = 1u << 9,  // QUADR (with SPLIT; the plan kernel's lookahead_block): the component is a per-step quadrature in
+                      //   quad lanes 2 / 3 (dyn.hpp step_fused kPosQuadr), no position broadcast in the stages; lanes 0 / 1
+                      //   hold garbage in x[0] and track, J = (J_X + J_Y) + act from lanes 2 and 3
 };
 // What DEFER returns in *dout: the reference is not known yet, so the lane stores its position
 // component after step k at dpos[k dstride] instead of accumulating the tracking term, and
@@ -96,12 +99,14 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
                                           DeferOut* dout = nullptr, const double* hp = nullptr,
                                           double cw = 0.0) {
   constexpr bool STAGE = F & kRStage, FAST = F & kRFast, SPLIT = F & kRSplit, ULDS = F & kRUlds;
-  constexpr bool TRAJ = F & kRTraj, S4 = F & kRS4, DEFER = F & kRDefer, CORR = F & kRCorr;
+  constexpr bool TRAJ = F & kRTraj, S4 = F & kRS4, DEFER = F & kRDefer, CORR = F & kRCorr, QUADR = F & kRQuadr;
+  constexpr int POS = QUADR ? kPosQuadr : (SPLIT ? kPosSplit : kPosBoth);   // dyn.hpp step_fused
   constexpr int XM = (F & kRXm) ? 1 : 0;
   static_assert(!DEFER || (SPLIT && S4), "deferred tracking cost: the controller's split, staged rollout");
   static_assert(!TRAJ || (INTEG != 0 && !SPLIT), "trajectory output: unscaled, unsplit state");
   static_assert(!S4 || (ULDS && FAST && !STAGE), "staged sincos / cost terms: the controller's fast rollout");
   static_assert(!SPLIT || (FAST && INTEG == 0 && LPM == 4), "position split: fused RK4 quads only");
+  static_assert(!QUADR || (SPLIT && !DEFER), "position quadrature: a split rollout that forms its own tracking term");
   static_assert(!ULDS || !STAGE, "candidates in LDS: unstaged rollout");
   static_assert(!CORR || (!SPLIT && !DEFER), "corridor term: a lane that holds both position components");
   static_assert(!CORR || (INTEG == 1 && LPM == 4 && !S4 && !XM), "corridor term: built for the NLP kernel's rollouts");
@@ -169,8 +174,8 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
     }
     const double d0 = ua - p0, d1 = ud - p1;          // nmpc.py:65-68
     if (!STAGE && !S4 && q.enforce) feas = (int)feas & (int)input_feasible(q, ua, ud, d0, d1);
-    if (FAST && INTEG == 0 && STAGE) step_fused<LPM, SPLIT>(sk, fq, x, fi, ud, K, dm);
-    else if (FAST && INTEG == 0) step_fused<LPM, SPLIT>(sk, fq, x, u, K, dm);
+    if (FAST && INTEG == 0 && STAGE) step_fused<LPM, POS>(sk, fq, x, fi, ud, K, dm);
+    else if (FAST && INTEG == 0) step_fused<LPM, POS>(sk, fq, x, u, K, dm);
     else if (FAST) step_fast<INTEG, LPM>(veh, t, sk, x, u, Ts, K, dm);
     else step<INTEG>(veh, t, x, u, Ts);
     if constexpr (CORR) pen = pen + corridor_slack2(hp + 6 * k, x[0], x[1]);
@@ -215,7 +220,10 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
   if (SPLIT) {                                                    // nmpc.py:48, :111
     const double e = x[0] - xr0;
     const double jl = e * (Pd * e) + track;                       // this component's part
-    J = (dpp_bcast<kQuad0>(jl) + dpp_bcast<kQuad1>(jl)) + act;    // X (lane 0) + Y (lane 1)
+    // X + Y: lanes 0 and 1, or (QUADR) lanes 2 and 3 — there lanes 0/1's jl is garbage (step_fused)
+    // and ends here: J, and with it `bad`, the count and the argmin, is the same in the four lanes
+    if constexpr (QUADR) J = (dpp_bcast<kQuad2>(jl) + dpp_bcast<kQuad3>(jl)) + act;
+    else J = (dpp_bcast<kQuad0>(jl) + dpp_bcast<kQuad1>(jl)) + act;
   } else {
     const double e0 = x[0] - xr0, e1 = x[1] - xr1;                 // nmpc.py:48 (xref_H)
     const double term = e0 * (q.P[0] * e0 + q.P[1] * e1) + e1 * (q.P[2] * e0 + q.P[3] * e1);
