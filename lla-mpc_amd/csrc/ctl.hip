@@ -1257,7 +1257,7 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
       sk.ch[0].nsB = 0.0;
     }
     const FusedK fq = make_fused(veh, sk, Ts, kScaled);
-    const fm::FmK K = fm::FmK::load<kLeanLA>();
+    const fm::FmK K = load_la_consts<0, LPM>();
     for (int j = 0; j < cpl; ++j) {
       const int cc = g + j * G;
       if (cc >= C) break;
@@ -1423,7 +1423,7 @@ __device__ __forceinline__ void ctl_spec(const CtlLaunch& c, int j, unsigned cha
       sk.ch[0].nsB = 0.0;
     }
     const FusedK fq = make_fused(veh, sk, Ts, kScaled);
-    const fm::FmK K = fm::FmK::load<kLeanLA>();
+    const fm::FmK K = load_la_consts<0, LPM>();
     const double Qd = sk.pc ? q.Q[3] : q.Q[0], Pd = sk.pc ? q.P[3] : q.P[0];
     // cpl == 1 with G == C (the host's layout for spec blocks): candidate g in quad g
     const int cc = g;

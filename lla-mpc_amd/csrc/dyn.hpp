@@ -265,9 +265,13 @@ __device__ __host__ __forceinline__ bool chain_static_ok(const Chain& c) {
 // ps = max |psi|.  ok(): hi in [2^-1000, 2^999] (a larger divisor's reciprocal may flush to
 // zero: a wrong finite angle; a smaller one — 0/0 at standstill — gives a NaN that the atan
 // core's min/max would swallow) and |psi| <= kSinCosMax (the fold's range).  The atan
-// divisor max(|z|, 1) needs no record: |z| > 2^1000 yields pi/2 exactly as atan does and an
-// infinite z a NaN that reaches the state (and, through the positions, the cost); the
-// callers re-run every lane whose result is not finite.  fmax/fmin skip a NaN operand, but
+// divisor needs no record.  Two-way form (max(|z|, 1): the precise cores and the LPM-1 lane):
+// |z| > 2^1000 yields pi/2 exactly as atan does and an infinite z a NaN that reaches the state
+// (and, through the positions, the cost); the callers re-run every lane whose result is not
+// finite.  Three-zone lean form (fastmath.hpp atan_zones: the quad and the lane pair): the
+// divisor is 1, |z| + 1 or |z|, never below 1, and |z| is clamped to 2^1000 ahead of it, so
+// every |z| >= 2^1000, z = +-inf included, gives +-pi/2 on the fast path — no NaN and no
+// re-run for an infinite z any more — while a NaN z still gives NaN (0 / 0 in its own zone).  fmax/fmin skip a NaN operand, but
 // a NaN operand comes from a NaN state, input or parameter and reaches the lane's result.
 struct Dom {
   double hi, lo, ps;
@@ -297,14 +301,14 @@ struct Dom {
 // caller records the lower bound itself (the LPM-1 lane: |den| once for both chains — the
 // divisor max(|yy|, |den|) is at least |den|, so min |den| >= 2^-1000 is a sufficient test,
 // stricter only at a standstill, which then takes the general path).
-template <bool LEAN = false, bool LO = true>
+template <bool LEAN = false, bool LO = true, bool SEL = true>
 __device__ __forceinline__ double chain_fast(const Chain& c, double den, double vy, double om,
                                              double dsel, Dom& dm, const fm::FmK& K) {
   const double yy = fma(c.lw, om, c.sg * vy);
   double h2;
-  const double a2 = fm::atan2_fast<LEAN>(yy, den, K, h2);
+  const double a2 = fm::atan2_fast<LEAN, SEL>(yy, den, K, h2);
   const double z = c.B * fma(-c.sg, a2, dsel);
-  const double at = fm::atan_fast<LEAN>(z, K);
+  const double at = fm::atan_fast<LEAN, SEL>(z, K);
   if constexpr (LO) dm.lo = fm::vmin(dm.lo, h2);
   dm.hi = fm::vmax(dm.hi, h2);
   return c.D * fm::sin_wide<LEAN>(c.C * at, K);
@@ -453,8 +457,9 @@ __device__ __forceinline__ StageF forces_fast(const StageK& sk, double den, doub
     f.Ffy = dpp_bcast<kPair0>(r);
     f.Fry = dpp_bcast<kPair1>(r);
   } else {
-    f.Ffy = chain_fast<LEAN, false>(sk.ch[0], den, vy, om, d, dm, K);
-    f.Fry = chain_fast<LEAN, false>(sk.ch[1], den, vy, om, 0.0, dm, K);
+    // the LPM-1 lane keeps the select fix-up and the two-way lean atan (fastmath.hpp chain_selects)
+    f.Ffy = chain_fast<LEAN, false, fm::chain_selects(1)>(sk.ch[0], den, vy, om, d, dm, K);
+    f.Fry = chain_fast<LEAN, false, fm::chain_selects(1)>(sk.ch[1], den, vy, om, 0.0, dm, K);
     dm.lo = fm::vmin_abs(den, dm.lo);
   }
   if constexpr (SCALED && LPM == 1) {
@@ -527,9 +532,18 @@ __device__ __forceinline__ Input make_input_fast(double a, double d, const fm::F
 // 456 instructions per step at LPM 4 (467 with 9 terms, 494 with the precise 10-term cores,
 // 507 in round 2), A/B 28.8 -> 27.2 us per tick with 9 terms (profiles/r03/ab_lean), 26.6
 // with 8 (profiles/r04/ab_lean8.log).  The plan kernel's staged quad loop is 461 instructions
-// per step with the position split and 440 with the position quadrature (step_fused
-// kPosQuadr, round 8: -4 fp64, -14 DPP moves, -3 s_nop).
+// per step with the position split, 440 with the position quadrature (step_fused
+// kPosQuadr, round 8: -4 fp64, -14 DPP moves, -3 s_nop) and 418 with the one-select octant
+// fix-up and the three-zone lean atan (fastmath.hpp octant_fix / atan_zones, round 9:
+// 2,132 -> 2,000 cycles per step).
 constexpr bool kLeanLA = true;
+// The FmK of a look-ahead rollout: the lean coefficient sets under the fused RK4 (INTEG 0), and
+// atan_zones' constants and the select words pinned where the lanes take them (fm::chain_selects).
+template <int INTEG, int LPM>
+__device__ __forceinline__ fm::FmK load_la_consts() {
+  constexpr bool kLean = kLeanLA && INTEG == 0;
+  return fm::FmK::load<kLean, kLean && fm::chain_selects(LPM)>();
+}
 
 struct FusedK {
   double h, hm, hIlf, hIlr, m1, m0, m2, m3;   // hm = h/m; m1 = hm k1, m0 = hm k0,

@@ -180,6 +180,8 @@ constexpr double kAtanR[10] = {
     -0.06649613695291669,  0.05736332165907643,  -0.04483334622272886,
     0.02275052699336167};
 constexpr double kTanPi8 = 0.41421356237309503;
+constexpr double kCotPi8 = 2.414213562373095;    // 1 + sqrt(2): the lean atan's zone III edge
+constexpr double kAtanClamp = 0x1p1000;          // the lean atan's largest divisor (atan_fast)
 // Lean cores of the look-ahead rollouts (kLeanLA): 8-term atan (1.1e-13 relative on |t| <=
 // tan(pi/8)) and 8-term sin_wide (2.6e-13 absolute to |a| = 3), and the division without its
 // residual correction (<= 18 ulp), against the <= 4 ulp of the precise cores, which the
@@ -228,13 +230,24 @@ constexpr double kSinWideMax = 3.0;   // sin(a) = a + a*s*QW(s) (10 terms, fit e
 struct FmK {
   double ar[10];
   double tp8, pio4;
+  double ctp8, zmax;                      // lean atan_fast: cot(pi/8), the clamp 2^1000
   double sw[10], sq[7], cq[7];
   double pio2, two_pi, cw0, cw1, cw2, sixth, six, rmagic, rmagic2, one;
   double inv_pi, inv_3pi;                 // (2/pi)/2, (2/pi)/6: the scaled yaw's RK4 weights
+  // Words of the select doubles (sel_one below): the high word of 1.0 and three zero low
+  // words, one per select double that is live at the same time in the lean atan (zs: sf, w and
+  // s2 in turn; zq: q3; zc: c1).  Pinned under load's PINS only: a select double is then ONE
+  // v_cndmask into the high half of a pair whose low half stays put, where the loop otherwise
+  // re-materialises 0x3ff00000 and a zero every step and copies the zero into two more pairs
+  // every stage (10 v_mov per LPM-4 step).  Not pinned, they are plain constants.
+  int hone, zs, zq, zc;
 
   __device__ __forceinline__ static void pin(double& x) { asm volatile("" : "+v"(x)); }
-  // LEAN: the kLeanTerms-term coefficient sets in ar / sw (the lean cores read no more)
-  template <bool LEAN = false>
+  __device__ __forceinline__ static void pin(int& x) { asm volatile("" : "+v"(x)); }
+  // LEAN: the kLeanTerms-term coefficient sets in ar / sw (the lean cores read no more);
+  // PINS: atan_zones' constants and the select words in VGPRs (the kernels whose lean atan is
+  // atan_zones: chain_selects; the others are then the code they were)
+  template <bool LEAN = false, bool PINS = LEAN>
   __device__ __forceinline__ static FmK load() {
     FmK k;
     constexpr int nA = LEAN ? kLeanTerms : 10;
@@ -244,6 +257,9 @@ struct FmK {
     k.pio4 = kPio4;
     pin(k.tp8);
     pin(k.pio4);
+    k.ctp8 = kCotPi8;
+    k.zmax = kAtanClamp;
+    if constexpr (PINS) { pin(k.ctp8); pin(k.zmax); }   // read by atan_zones only
 #pragma unroll
     for (int i = 0; i < nA; ++i) { k.sw[i] = LEAN ? kSinWQL[i] : kSinWQ[i]; pin(k.sw[i]); }
 #pragma unroll
@@ -268,6 +284,9 @@ struct FmK {
     k.inv_pi = kTwoOverPi * 0.5;
     k.inv_3pi = kTwoOverPi / 6.0;
     pin(k.inv_pi); pin(k.inv_3pi);
+    k.hone = 0x3FF00000;
+    k.zs = k.zq = k.zc = 0;
+    if constexpr (PINS) { pin(k.hone); pin(k.zs); pin(k.zq); pin(k.zc); }
     return k;
   }
 };
@@ -352,11 +371,41 @@ __device__ __forceinline__ double vmin_abs2(double a, double b) {  // min(|a|, |
 template <bool LEAN = false>
 __device__ __forceinline__ double atan_ratio_k(double n, double d, const FmK& K) {
   const bool red = n > K.tp8 * d;
-  const double sf = __hiloint2double(red ? 0x3FF00000 : 0, 0);
+  const double sf = __hiloint2double(red ? K.hone : 0, K.zs);
   const double t = div_fast<LEAN>(fma(-sf, d, n), fma(sf, n, d));
   const double s = t * t;
   return fma(sf, K.pio4, fma(t * s, horner<LEAN ? kLeanTerms : 10>(K.ar, s), t));
 }
+
+// The octant fix-up of the two-way cores up to its sign: swap ? pi/2 - r : -r as ONE high-word
+// select and an FMA, w = 1.0 or 0.0 (like sf above).  w = 1 is the same single rounding of
+// pi/2 - r, w = 0 gives -r exactly; r >= 0 and pi/2 - r >= 0, and the callers' copysign (a
+// v_bfi) discards the sign, so the result has the bits of copysign(swap ? pi/2 - r : r, y)
+// — without the compare's 64-bit select (two v_cndmask) on the chain.
+// FMA = false: the select form, bit for bit the same value (the LPM-1 lane, chain_selects
+// below).  -DLLAMPC_AB_FIXUP_SELECT builds the select form everywhere (A/B builds only).
+template <bool FMA = true>
+__device__ __forceinline__ double octant_fix(bool swap, double r, const FmK& K) {
+#ifdef LLAMPC_AB_FIXUP_SELECT
+  return swap ? K.pio2 - r : r;
+#else
+  if constexpr (!FMA) return swap ? K.pio2 - r : r;
+  const double w = __hiloint2double(swap ? K.hone : 0, K.zs);
+  return fma(w, K.pio2, -r);
+#endif
+}
+
+// Which rollouts take the forms above and atan_zones below (the SEL argument of the cores and
+// of dyn.hpp chain_fast): the quad and the lane pair (LPM 4 / 2: a wave or less per SIMD, where
+// every instruction of the serial stream costs its issue slot and its latency).  The LPM-1
+// lane, the throughput regime, keeps the select fix-up and the two-way lean atan, so that
+// plan_rk4_l1.hip compiles to the instructions it had: atan_zones' constants and select doubles
+// spill 20 bytes per lane of the work-queue kernels' 256 VGPRs to scratch, and the C = 64 tick
+// measured slower in every build that changed those kernels — with both forms (+0.65 %), with
+// the FMA fix-up alone (+0.9 %: 15 instructions fewer per step, no scratch) and with nothing but
+// eight more constant moves ahead of the parent's loop (+2.3 %): DESIGN.md §3,
+// profiles/r09/chain_selects.
+constexpr bool chain_selects(int lpm) { return lpm != 1; }
 
 // atan2(y, x) for x >= 0 on the domain atan2_fast_ok(y, x): the sum |y| + x in
 // [2^-1000, 2^1000] (so max(|y|, x) is a safe divisor; NaN -> not ok).
@@ -367,36 +416,73 @@ __device__ __host__ __forceinline__ bool atan2_fast_ok(double y, double x) {
 // hi = max(|y|, |x|), the divisor: hi in [2^-1000, 2^999] lies inside the domain (the
 // rollout checks its running extremes once, dyn.hpp Dom).  x enters as |x| (the callers'
 // x is |vx| or the clamped vx >= vmin, so passing vx itself saves materialising |vx|).
-template <bool LEAN = false>
+template <bool LEAN = false, bool SEL = true>
 __device__ __forceinline__ double atan2_fast(double y, double x, const FmK& K, double& hi) {
   const double ay = fabs(y);
   hi = vmax_abs2(y, x);
   const double r = atan_ratio_k<LEAN>(vmin_abs2(y, x), hi, K);
-  const double o = (ay > fabs(x)) ? K.pio2 - r : r;   // no pi/2 tail: <= 2 ulp (measured)
-  return copysign(o, y);
+  return copysign(octant_fix<SEL>(ay > fabs(x), r, K), y);   // no pi/2 tail: <= 2 ulp (measured)
 }
-template <bool LEAN = false>
+template <bool LEAN = false, bool SEL = true>
 __device__ __forceinline__ double atan2_fast(double y, double x, const FmK& K) {
   double hi;
-  return atan2_fast<LEAN>(y, x, K, hi);
+  return atan2_fast<LEAN, SEL>(y, x, K, hi);
 }
 
 // atan(z) on the domain |z| <= 2^1000: the reciprocal branch as a division by max(|z|, 1)
 // (exact when |z| <= 1).
 __device__ __host__ __forceinline__ bool atan_fast_ok(double z) { return fabs(z) <= 0x1p1000; }
-// hz = max(|z|, 1), the divisor: hz <= 2^1000 is the domain.
-template <bool LEAN = false>
+// The lean atan in three zones (-DLLAMPC_AB_ATAN_TWOWAY builds the two-way form below for the
+// lean cores too; A/B builds only).
+#ifdef LLAMPC_AB_ATAN_TWOWAY
+constexpr bool kAtanZones = false;
+#else
+constexpr bool kAtanZones = true;
+#endif
+// Lean atan(z), a = |z|: one operand of the two-way form's ratio min(a, 1) / max(a, 1) is
+// always exactly 1, so the reduced argument t and the offset follow from a directly:
+//   I    a <= tan(pi/8)              t = a / 1            offset 0
+//   II   tan(pi/8) < a <= cot(pi/8)  t = (a - 1)/(a + 1)  offset pi/4
+//   III  a > cot(pi/8)               t = -1 / a           offset pi/2
+// as num = q3 a - s2, den = s2 a + q3, offset c1 pi/4 with the select doubles s2 = (a > tp8),
+// q3 = !(a > ctp8) (1.0 or 0.0) and c1 = 0, 1 or 2 — high-word selects, as sf in atan_ratio_k.
+// The polynomial is odd, so the sign of t carries the two-way form's "pi/2 - .": no v_max,
+// v_min, tp8 d product, swap select or second offset FMA.  Against the two-way lean atan the
+// value moves by at most one rounding of the reconstruction (zone II with a > 1: pi/4 + p(t)
+// for pi/2 - (pi/4 + p(-t))).
+// The divisor is 1, a + 1 or a: never below 1, so no lower domain bound.  Above, a is clamped
+// to 2^1000 (one v_min): every |z| >= 2^1000 — infinity too — gives +-pi/2 with a normal
+// reciprocal, where the two-way form has a NaN for z = +-inf.  (Without the clamp an infinite
+// a makes 0 * inf in num and rcp(inf) * inf in the Newton step.)  The zone compares read z
+// itself, and III is taken as !(a <= ctp8): a NaN z is then in III but not in II — num = den =
+// 0, and 0 / 0 returns the NaN that the clamp's v_min would have dropped.
+// hz = the divisor, in [1, 2^1000 + 1].
+__device__ __forceinline__ double atan_zones(double z, const FmK& K, double& hz) {
+  const double a = vmin_abs(z, K.zmax);
+  const bool z2 = fabs(z) > K.tp8, z3 = !(fabs(z) <= K.ctp8);
+  const int h2 = z2 ? K.hone : 0;
+  const double s2 = __hiloint2double(h2, K.zs);
+  const double q3 = __hiloint2double(z3 ? 0 : K.hone, K.zq);
+  const double c1 = __hiloint2double(z3 ? 0x40000000 : h2, K.zc);   // 2.0: an inline constant
+  hz = fma(s2, a, q3);
+  const double t = div_fast<true>(fma(q3, a, -s2), hz);
+  const double s = t * t;
+  return copysign(fma(c1, K.pio4, fma(t * s, horner<kLeanTerms>(K.ar, s), t)), z);
+}
+// hz = max(|z|, 1), the divisor: hz <= 2^1000 is the domain.  (LEAN with SEL: atan_zones,
+// every z.)
+template <bool LEAN = false, bool SEL = true>
 __device__ __forceinline__ double atan_fast(double z, const FmK& K, double& hz) {
+  if constexpr (LEAN && SEL && kAtanZones) return atan_zones(z, K, hz);
   const double az = fabs(z);
   hz = vmax_abs(z, K.one);
   const double r = atan_ratio_k<LEAN>(vmin_abs(z, K.one), hz, K);
-  const double o = (az > 1.0) ? K.pio2 - r : r;   // no pi/2 tail: <= 2 ulp (measured)
-  return copysign(o, z);
+  return copysign(octant_fix<SEL>(az > 1.0, r, K), z);   // no pi/2 tail: <= 2 ulp (measured)
 }
-template <bool LEAN = false>
+template <bool LEAN = false, bool SEL = true>
 __device__ __forceinline__ double atan_fast(double z, const FmK& K) {
   double hz;
-  return atan_fast<LEAN>(z, K, hz);
+  return atan_fast<LEAN, SEL>(z, K, hz);
 }
 
 // Two independent reduced-ratio atans with ONE reciprocal (the LPM-1 lane's front and rear
@@ -433,10 +519,8 @@ __device__ __forceinline__ void atan2_fast_pair(double yf, double yr, double x, 
   hr = vmax_abs2(yr, x);
   double rf, rr;
   atan_ratio_pair(vmin_abs2(yf, x), hf, vmin_abs2(yr, x), hr, K, rf, rr, dprod);
-  const double of = (fabs(yf) > fabs(x)) ? K.pio2 - rf : rf;
-  const double orr = (fabs(yr) > fabs(x)) ? K.pio2 - rr : rr;
-  af = copysign(of, yf);
-  ar = copysign(orr, yr);
+  af = copysign(octant_fix(fabs(yf) > fabs(x), rf, K), yf);
+  ar = copysign(octant_fix(fabs(yr) > fabs(x), rr, K), yr);
 }
 
 // atan(z_f) and atan(z_r) by atan_ratio_pair; dprod = the product of the divisors
@@ -446,10 +530,8 @@ __device__ __forceinline__ void atan_fast_pair(double zf, double zr, const FmK& 
   double rf, rr;
   atan_ratio_pair(vmin_abs(zf, K.one), vmax_abs(zf, K.one), vmin_abs(zr, K.one),
                   vmax_abs(zr, K.one), K, rf, rr, dprod);
-  const double of = (fabs(zf) > 1.0) ? K.pio2 - rf : rf;
-  const double orr = (fabs(zr) > 1.0) ? K.pio2 - rr : rr;
-  af = copysign(of, zf);
-  ar = copysign(orr, zr);
+  af = copysign(octant_fix(fabs(zf) > 1.0, rf, K), zf);
+  ar = copysign(octant_fix(fabs(zr) > 1.0, rr, K), zr);
 }
 
 // sin(a) for |a| <= kSinWideMax, one polynomial (the Pacejka argument C*atan(.) is

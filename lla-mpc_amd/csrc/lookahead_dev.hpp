@@ -283,7 +283,7 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
   fm::FmK K0;
   double up0, up1;
   if constexpr (!kBatch) {
-    if constexpr (!XM) K0 = fm::FmK::load<kLeanLA && INTEG == 0>();
+    if constexpr (!XM) K0 = load_la_consts<INTEG, LPM>();
     if (STAGE) {
       const fm::FmK K = [&] {
         if constexpr (XM) return fm::FmK::load();
@@ -339,7 +339,7 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
     double sua = 0.0, sdl = 0.0, sp0 = 0.0, sp1 = 0.0;
     if (STAGE) stage_load(tid, sua, sdl, sp0, sp1);
     // under the loads' latency: the polynomial constants, the pins, this lane's model
-    K0 = fm::FmK::load<kLeanLA && INTEG == 0>();
+    K0 = load_la_consts<INTEG, LPM>();
     pin_consts();
     model_setup();
     for (int e = tid; e <= H; e += BT) {               // one pass unless H >= BT
@@ -509,7 +509,7 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
   if (live) {
     if constexpr (!kBatch) model_setup();   // the batched prologue: ahead of the barrier
     const fm::FmK K = [&] {
-      if constexpr (XM) return fm::FmK::load<kLeanLA && INTEG == 0>();
+      if constexpr (XM) return load_la_consts<INTEG, LPM>();
       else return K0;
     }();
     for (int j = 0; j < cpl; ++j) {
