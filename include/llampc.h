@@ -431,6 +431,14 @@ int llampc_ctl_set_exchange(llampc_ctl* ctl, llampc_mailbox* mb, const double* g
 int llampc_ctl_set_gather(llampc_ctl* ctl, int32_t world, int32_t rank, llampc_comm* comm, const double* gparams,
                           int64_t n_global);
 int32_t llampc_ctl_record_words(int32_t K);
+/* The launch shape of a controller tick past the warm-up with n models, a raceline of rl_n knots
+ * and no exchange — host only, no device needed (for tests that mean to run one variant):
+ * out = {lpm (look-ahead lanes per rollout: 4, 2 or 1), G (lanes per model), cpl (candidates per
+ * lane), mpb (models per look-ahead block), s4 (1: the look-ahead's input terms are staged in LDS;
+ * honours LLAMPC_CTL_NO_STAGE as llampc_ctl_create does), zfit (1: the candidates' variates are
+ * pre-loaded per thread), R (look-back models per lane), nb_lb, nb_la (look-back / look-ahead
+ * blocks)}.  LLAMPC_E_ARG for a shape llampc_ctl_create refuses. */
+int llampc_ctl_variant(int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl_n, int32_t out[9]);
 int llampc_ctl_shard_record(llampc_ctl* ctl, uint64_t* words /* [llampc_ctl_record_words(K)] */, int32_t* nw);
 int llampc_ctl_resume(llampc_ctl* ctl, const uint64_t* all_words /* [world][nw] */);
 /* The sharded controller's merge on the host (the device exchange runs the same functions,

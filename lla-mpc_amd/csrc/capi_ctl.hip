@@ -318,15 +318,8 @@ static int ctl_prepare(llampc_ctl* c, const double* x_t, llampc_ctl::Prep& P) {
     L.br_walk = mu_bracket(b->rl_mus.data(), b->rl_M, L.use_mu ? c->hint_mu : L.mu_fixed);   // rt.py:278-282
   }
   L.full = full;
-  L.nslots = warm ? 1 : k.K + 1;
-  L.G = lookahead_group(k.C);
-  L.cpl = (k.C + L.G - 1) / L.G;
-  const int lpm = 4 * L.G <= kBlock ? 4 : (2 * L.G <= kBlock ? 2 : 1);
-  L.mpb = kBlock / (L.G * lpm);
   L.S = k.S;
   L.K = k.K;
-  L.nb_lb = L.fin.nb_lb;
-  L.nb_la = (L.nslots + L.mpb - 1) / L.mpb;
   // sharded: the exchange runs on every tick whose window is full (the same ticks on every
   // rank); the selection is global, the look-ahead reads the replicated global table
   L.sel_goff = b->goff;
@@ -358,14 +351,19 @@ static int ctl_prepare(llampc_ctl* c, const double* x_t, llampc_ctl::Prep& P) {
     L.px_gath = c->d_xgath.get();
     L.px_bound = 16;                     // ~10 ms: the records are there when the launch starts
   }
-  // the look-ahead blocks stage every (candidate, step)'s input terms when they fit in LDS
-  // (CtlLaunch.s4; LLAMPC_CTL_NO_STAGE=1 at create: never, for A/B runs)
-  size_t poll_s4 = 0;
-  const size_t lds_s4 = ctl_lds_bytes(k.H, k.C, b->rl_n, L.nb_lb, k.K, &poll_s4, true, L.px_G);
-  L.s4 = (!c->no_stage && lds_s4 <= 160 * 1024) ? 1 : 0;
-  size_t lds = L.s4 ? lds_s4 : ctl_lds_bytes(k.H, k.C, b->rl_n, L.nb_lb, k.K, &L.poll_off, false, L.px_G);
-  if (lds > 160 * 1024) return fail(LLAMPC_E_ARG, "controller tick needs %zu B of LDS (> 160 KiB)", lds);
-  if (L.s4) L.poll_off = poll_s4;
+  // the launch's shape (capi_host.hpp ctl_shape: the lane split, the staging, the block counts)
+  const CtlShape V = ctl_shape(b->n, k.C, k.H, k.K, b->rl_n, warm, do_lb, c->no_stage, L.px_G);
+  const int lpm = V.lpm;
+  L.nslots = V.nslots;
+  L.G = V.G;
+  L.cpl = V.cpl;
+  L.mpb = V.mpb;
+  L.nb_lb = V.nb_lb;
+  L.nb_la = V.nb_la;
+  L.s4 = V.s4;
+  L.poll_off = V.poll_off;
+  size_t lds = V.lds;
+  if (lds > kCtlLdsMax) return fail(LLAMPC_E_ARG, "controller tick needs %zu B of LDS (> 160 KiB)", lds);
   // the speculative look-ahead (CtlLaunch.n_spec): armed ticks past the warm-up whose rollouts
   // are one model per block in fused quads with diagonal Q / P (the spec blocks' layout)
   {
@@ -729,6 +727,26 @@ int llampc_ctl_set_exchange(llampc_ctl* c, llampc_mailbox* mb, const double* gpa
 }
 
 int32_t llampc_ctl_record_words(int32_t K) { return (K < 1 || K > LLAMPC_KMAX) ? 0 : ctl_rec_words(K); }
+
+// The shape ctl_prepare gives a tick past the warm-up (unsharded), from the same ctl_shape.
+int llampc_ctl_variant(int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl_n, int32_t out[9]) {
+  if (!out) return fail(LLAMPC_E_ARG, "NULL argument");
+  // C beyond kCtlVariantCMax: the candidates alone (16 B each per step) exceed the CU's LDS, and the
+  // int products C * H below stay far from overflow
+  constexpr int32_t kCtlVariantCMax = 1 << 16;
+  if (n < 1 || C < 1 || C > kCtlVariantCMax || H < 1 || H > LLAMPC_HMAX || K < 1 || K > LLAMPC_KMAX || rl_n < 2)
+    return fail(LLAMPC_E_ARG, "n=%lld C=%d (1..%d) H=%d (1..%d) K=%d (1..%d) rl_n=%d", (long long)n, C, kCtlVariantCMax,
+                H, LLAMPC_HMAX, K, LLAMPC_KMAX, rl_n);
+  bool no_stage = false;
+  if (const char* e = std::getenv("LLAMPC_CTL_NO_STAGE")) no_stage = e[0] == '1';
+  const CtlShape V = ctl_shape(n, C, H, K, rl_n, false, true, no_stage, 0);
+  if (V.lds > kCtlLdsMax)                // llampc_ctl_create refuses the shape
+    return fail(LLAMPC_E_ARG, "controller tick needs %zu B of LDS (> 160 KiB): C*H=%d too large for this track", V.lds,
+                C * H);
+  const int32_t v[9] = {V.lpm, V.G, V.cpl, V.mpb, V.s4, V.zfit, V.R, V.nb_lb, V.nb_la};
+  std::memcpy(out, v, sizeof v);
+  return LLAMPC_OK;
+}
 
 int llampc_ctl_set_gather(llampc_ctl* c, int32_t world, int32_t rank, llampc_comm* comm, const double* gparams,
                           int64_t n_global) {

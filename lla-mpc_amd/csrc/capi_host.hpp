@@ -229,6 +229,43 @@ inline void bank_final(const BankView& b, FinalLaunch& f) {
   f.tk_idx = b.tk_idx;
 }
 
+// The launch shape of a controller tick (ctl.hip ctl_kernel<lpm, *>): the look-ahead's lanes per
+// rollout, lane group, candidates per lane and models per block, whether its input terms are
+// staged (s4: the staged layout fits the CU's 160 KiB and LLAMPC_CTL_NO_STAGE is off) and its
+// variates pre-drawn (zfit), the look-back's models per lane and the block counts, with the
+// launch's LDS bytes and the completing block's area offset.  The one statement of the rule: the
+// launch (capi_ctl.hip ctl_prepare) and llampc_ctl_variant both take it from here.
+struct CtlShape {
+  int lpm, G, cpl, mpb, s4, zfit, R, nb_lb, nb_la, nslots;
+  size_t lds, poll_off;
+};
+constexpr size_t kCtlLdsMax = 160 * 1024;
+inline CtlShape ctl_shape(int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl_n, bool warm, bool do_lb,
+                          bool no_stage, int px_G) {
+  CtlShape s{};
+  s.R = lookback_r(n, K);
+  s.nb_lb = do_lb ? lookback_blocks_r(n, s.R) : 1;
+  s.nslots = warm ? 1 : K + 1;
+  s.G = lookahead_group(C);
+  s.cpl = (C + s.G - 1) / s.G;
+  s.lpm = 4 * s.G <= kBlock ? 4 : (2 * s.G <= kBlock ? 2 : 1);
+  s.mpb = kBlock / (s.G * s.lpm);
+  s.nb_la = (s.nslots + s.mpb - 1) / s.mpb;
+  s.zfit = ctl_zfit(C, H) ? 1 : 0;
+  // the look-ahead blocks stage every (candidate, step)'s input terms when they fit in LDS
+  // (CtlLaunch.s4; LLAMPC_CTL_NO_STAGE=1 at create: never, for A/B runs)
+  size_t poll_s4 = 0;
+  const size_t lds_s4 = ctl_lds_bytes(H, C, rl_n, s.nb_lb, K, &poll_s4, true, px_G);
+  s.s4 = (!no_stage && lds_s4 <= kCtlLdsMax) ? 1 : 0;
+  if (s.s4) {
+    s.lds = lds_s4;
+    s.poll_off = poll_s4;
+  } else {
+    s.lds = ctl_lds_bytes(H, C, rl_n, s.nb_lb, K, &s.poll_off, false, px_G);
+  }
+  return s;
+}
+
 // Spins until *tag == want (acquire): 0.  A tag that `stop` accepts ends the spin with
 // kSpinStopped.  After `bound`, on_timeout() runs once (it synchronises the stream, so a HIP
 // error is the one reported: its non-zero return, an LLAMPC_E_* code, is passed on as it is); a

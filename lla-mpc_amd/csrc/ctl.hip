@@ -1047,9 +1047,9 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
   CTL_STAMP(blockIdx.x, 14);
   // waves 1-3: this tick's candidate variates (the previous tick's completion drew them) are
   // loaded now, their latency under the tables' (used only when their tag matches: ctl_draw)
-  constexpr int kZPre = 16;
+  constexpr int kZPre = kCtlZPre;
   const int CH = C * H;
-  const bool zfit = c.znoise != nullptr && CH <= kZPre * (kBlock - 64);
+  const bool zfit = c.znoise != nullptr && ctl_zfit(C, H);
   double zr[kZPre][2];
   if (tid >= 64 && zfit) {
     const double* zb = c.znoise + 2 * (size_t)CH * (int)(c.tick & 1);

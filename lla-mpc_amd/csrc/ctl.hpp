@@ -21,6 +21,10 @@ namespace llampc {
 constexpr int kCtlSlotsMax = LLAMPC_KMAX + 1;   // look-ahead models: top-K + the selection
 constexpr int kCtlSMax = 64;                    // mu-hat smoothing window (rt.py:68 uses 20)
 constexpr int kCtlSegs = 9;                     // project_fast over raceline[:, p:p+10]
+// The look-ahead blocks' waves 1-3 hold at most kCtlZPre (candidate, step) pairs of pre-drawn
+// variates per thread: beyond that the candidates are drawn in the launch on every tick.
+constexpr int kCtlZPre = 16;
+__host__ __device__ constexpr bool ctl_zfit(int C, int H) { return C * H <= kCtlZPre * (kBlock - 64); }
 
 // Device-resident controller state, written by the block that completes a tick and read by
 // the next tick's blocks (stream order between the launches).

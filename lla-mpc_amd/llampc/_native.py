@@ -158,6 +158,7 @@ _SIGNATURES = {
     "llampc_ctl_set_exchange": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_int64]),
     "llampc_ctl_set_gather": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _dp, C.c_int64]),
     "llampc_ctl_record_words": (C.c_int32, [C.c_int32]),
+    "llampc_ctl_variant": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "llampc_ctl_shard_record": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "llampc_ctl_resume": (C.c_int, [C.c_void_p, C.c_void_p]),
     "llampc_ctl_set_prelaunch": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -241,6 +242,18 @@ def plan_variant(n: int, C_: int, H: int, integrator="rk4", share: int = 1) -> d
     integ = INTEGRATORS[integrator] if isinstance(integrator, str) else int(integrator)
     check(load().llampc_plan_variant(int(n), int(C_), int(H), integ, int(share), out))
     return dict(lpm=out[0], G=out[1], cpl=out[2], stage=bool(out[3]))
+
+
+CTL_VARIANT_FIELDS = ("lpm", "G", "cpl", "mpb", "s4", "zfit", "R", "nb_lb", "nb_la")
+
+
+def ctl_variant(n: int, C_: int, H: int, K: int, rl_n: int) -> dict:
+    """The launch shape of a controller tick past the warm-up (llampc_ctl_variant; host only, reads
+    LLAMPC_CTL_NO_STAGE as llampc_ctl_create does): {lpm, G, cpl, mpb, s4, zfit, R, nb_lb, nb_la}.
+    Raises NativeError (E_ARG) for a shape the controller refuses at create."""
+    out = (C.c_int32 * 9)()
+    check(load().llampc_ctl_variant(int(n), int(C_), int(H), int(K), int(rl_n), out))
+    return dict(zip(CTL_VARIANT_FIELDS, (int(v) for v in out)))
 
 
 def dptr(a: np.ndarray | None):

@@ -419,7 +419,9 @@ class LLAMPC:
         self.mu = MuEstimator(mass=sh["mass"], lf=sh["lf"], lr=sh["lr"], mu_init=mu_init, S=S, alpha=alpha)
         self.cost = cost if cost is not None else nat.cost_struct(enforce_bounds=True)
         self.integrator = integrator
-        self.gen = CandidateGenerator(C, H, Ts, seed=seed)
+        # host mode's sampler (NumPy's RandomState: a 32-bit seed); the device draws its own (Philox,
+        # 64-bit), so device mode accepts the seeds the host sampler cannot take and then has none
+        self.gen = CandidateGenerator(C, H, Ts, seed=seed) if mode == "host" or 0 <= int(seed) < 2 ** 32 else None
         self.nan_policy = nan_policy
         self._last = self._last_full = None
         self._u_seq_host = self._u_prev_host = self._topk_host = None
