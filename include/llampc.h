@@ -164,7 +164,9 @@ int llampc_bank_info(const llampc_bank* bank, int64_t* n, int64_t* global_offset
                      int32_t* W, int32_t* window_count, int32_t* device);
 int llampc_bank_reset(llampc_bank* bank);                 /* empty the window       */
 /* plan-kernel launches enqueued on this bank so far (every tick entry point is ONE
- * launch; the controller test counts them — replaces nothing in the reference) */
+ * launch; the controller test counts them — replaces nothing in the reference).  On an NLP
+ * solver's bank: its solve launches, and every track-corridor kernel (llampc_nlp_solve_track,
+ * llampc_nlp_track_corridor) as one more */
 int llampc_bank_launches(const llampc_bank* bank, int64_t* launches);
 /* ring: [n][W] oldest -> newest (the rt.py error_windows layout, zeros if unfilled) */
 int llampc_bank_window(llampc_bank* bank, double* ring, int32_t* window_count);
@@ -193,8 +195,9 @@ int llampc_bank_set_concurrency(llampc_bank* bank, int32_t banks);
  * multi-GPU exchange, with the events' cost on 1/k of the ticks); enable=0 disarms.
  * count = launches timed. */
 int llampc_bank_timing(llampc_bank* bank, int32_t enable, int32_t max_launches);
-/* Synchronises, returns avg_ms[3] and count[3] for {plan kernel, reserved, reserved}
- * since the last read, and re-arms the counters. */
+/* Synchronises, returns avg_ms[3] and count[3] for {plan kernel, the NLP solver's track-corridor
+ * kernel (llampc_nlp_track_corridor, llampc_nlp_solve_track), reserved} since the last read, and
+ * re-arms the counters. */
 int llampc_bank_timing_read(llampc_bank* bank, double* avg_ms, int64_t* count);
 
 /* ---- look-back (host pointers) -------------------------------------------------- */
@@ -491,6 +494,39 @@ int llampc_nlp_solve(llampc_nlp* nlp, const double* x0, const double* xref, cons
 int llampc_nlp_solve_corridor(llampc_nlp* nlp, const double* x0, const double* xref, const double* uprev,
                               const double* base, int32_t has_hold, const double* hp, double weight,
                               double* umpc, double* fval, double* xmpc, double* max_slack);
+/* The track for the device-built corridor: the centre line centre [2][n] (x row, y row), the arc
+ * length theta [n] at every centre point and the closed length, as the Track object holds them
+ * (center_line, theta_track, track_length: they are NOT recomputed here, NumPy's sums round in
+ * their own order), and the track's width.  Copies the tables to the device; a second call replaces
+ * the track.  LLAMPC_E_ARG: n outside [2, 4096], a non-finite value, theta[0] != 0 or theta not
+ * strictly increasing, track_length <= theta[n-1] or <= 0.2 (four times the tangent's 0.05 m arc
+ * step), track_width <= 0.  Blocking. */
+int llampc_nlp_set_track(llampc_nlp* nlp, const double* centre /* [2][n] */, const double* theta /* [n] */,
+                         int32_t n, double track_length, double track_width);
+/* The track's corridor along a path on the device (csrc/corridor_dev.hpp, one small kernel):
+ * path [2][H+1] = P_0 .. P_H with the solver's H (P_0 is not read) -> hp [H][6], row k - 1 the two
+ * half-planes |n.(p - c)| <= track_width / 2 - margin across the centre line at P_k's nearest point
+ * (llampc.mpc.constraints.track_corridor in scalar form: nearest segment of the closed centre line,
+ * ties to the lower one; the tangent from the centre line 0.05 m of arc length either side), and
+ * theta [H] (may be NULL), that point's arc length.  The centre-line lookup extrapolates the last
+ * segment over the closing gap, as Track.param_to_xy does, and is discontinuous at vertex 0.
+ * LLAMPC_E_STATE with no track set; LLAMPC_E_ARG, with nothing launched: a non-finite path entry, a
+ * margin that is not finite or >= track_width / 2.  Blocking (as llampc_ctl_reference is the
+ * controller's reference alone, this is the corridor alone). */
+int llampc_nlp_track_corridor(llampc_nlp* nlp, const double* path /* [2][H+1] */, double margin,
+                              double* hp /* [H][6] */, double* theta /* [H], may be NULL */);
+/* llampc_nlp_solve_corridor with the track's corridor along `path`, built on the device: the
+ * corridor kernel, then the corridor solve's launch on the bank's stream, with no host
+ * synchronisation between the two and one completion wait, as every solve.  The kernel writes hp
+ * into the solver's pinned mapped buffer, where the solve reads it and where the host reads it
+ * after the completion tag: -> max_slack (may be NULL) of the returned xmpc on it, hp_out [H][6]
+ * (may be NULL) a copy.  LLAMPC_E_STATE and LLAMPC_E_ARG as llampc_nlp_track_corridor, LLAMPC_E_ARG
+ * also for a weight negative or non-finite; LLAMPC_E_DEVICE if the read-back corridor is not a
+ * valid one.  Blocking. */
+int llampc_nlp_solve_track(llampc_nlp* nlp, const double* x0, const double* xref, const double* uprev,
+                           const double* base, int32_t has_hold, const double* path /* [2][H+1] */,
+                           double margin, double weight, double* umpc, double* fval, double* xmpc,
+                           double* max_slack, double* hp_out /* [H][6], may be NULL */);
 int llampc_nlp_destroy(llampc_nlp* nlp);
 
 /* ---- raw batched dynamics (Dynamic API parity) ---------------------------------- */

@@ -2,7 +2,11 @@
 // nlp.hip): CEM iterations enqueued back to back on the bank's stream, the Euler trajectory of
 // the best sequence, the result through pinned host memory.  The corridor solve
 // (llampc_nlp_solve_corridor) is the same solve with the half-planes handed over in a pinned mapped
-// buffer and the largest slack of the returned trajectory computed here on the host.
+// buffer and the largest slack of the returned trajectory computed here on the host.  With a track
+// set (llampc_nlp_set_track: the centre line's tables, uploaded once) llampc_nlp_solve_track builds
+// those half-planes on the device instead: track_corridor_kernel (kernels.hip, corridor_dev.hpp)
+// writes them into the same buffer, enqueued ahead of the corridor solve on the same stream with no
+// host synchronisation between the two; llampc_nlp_track_corridor is that kernel alone.
 #include "capi_common.hpp"
 
 using namespace llampc;
@@ -24,8 +28,13 @@ struct __attribute__((visibility("hidden"))) llampc_nlp {
                                          // LLAMPC_NLP_RERUN_TRAJ=1 at create: always re-run, tests)
   MappedRecord<NlpResult> host;          // the last round writes the result, then the solve's number
   Mapped<double> hp;                     // the corridor solve's half-planes [HMAX][6] (NlpCorridor.hp):
-                                         // pinned and mapped, written by the host before the launch,
-                                         // read once per block and launch (no H2D copy)
+                                         // pinned and mapped, written by the host before the launch
+                                         // or by track_corridor_kernel ahead of it, read once per
+                                         // block and launch (no H2D copy); then that kernel's
+                                         // theta [HMAX]
+  DevBuf<double> d_track;                // llampc_nlp_set_track: cx | cy | tt, [3][tr_n]
+  int32_t tr_n = 0;                      // 0: no track set
+  double tr_L = 0.0, tr_width = 0.0;
   bool ltraj_cor = false;                // ltraj of a corridor solve (its LDS holds the half-planes too)
   uint64_t calls = 0;
   std::mutex mu;
@@ -64,7 +73,7 @@ int llampc_nlp_create(llampc_bank* b, const llampc_nlp_cfg* cfg, llampc_nlp** ou
   // Tagged words start at tag 0, which no solve uses (nlp_seq of a solve number >= 1)
   if ((rc = p->d_st.zalloc(1)) || (rc = p->d_cost.zalloc((size_t)k.samples * (6 + 4 * H))) ||
       (rc = p->d_ms_tag.zalloc(8 * (size_t)LLAMPC_HMAX)) || (rc = p->host.alloc("NLP result")) ||
-      (rc = p->hp.alloc(6 * (size_t)LLAMPC_HMAX, "NLP corridor")))
+      (rc = p->hp.alloc(7 * (size_t)LLAMPC_HMAX, "NLP corridor")))
     return rc;
   {
     // every round in one launch needs all samples / 64 blocks resident together (each waits for
@@ -83,13 +92,78 @@ int llampc_nlp_create(llampc_bank* b, const llampc_nlp_cfg* cfg, llampc_nlp** ou
   return LLAMPC_OK;
 }
 
+int llampc_nlp_set_track(llampc_nlp* p, const double* centre, const double* theta, int32_t n, double track_length,
+                         double track_width) {
+  if (!p || !centre || !theta) return fail(LLAMPC_E_ARG, "NULL argument");
+  if (n < 2 || n > kTrackMaxPoints) return fail(LLAMPC_E_ARG, "n=%d outside [2, %d]", n, kTrackMaxPoints);
+  for (int64_t i = 0; i < 2 * (int64_t)n; ++i)
+    if (!std::isfinite(centre[i])) return fail(LLAMPC_E_ARG, "centre line: entry %lld is not finite", (long long)i);
+  if (!std::isfinite(track_length) || !std::isfinite(track_width)) return fail(LLAMPC_E_ARG, "length / width not finite");
+  if (theta[0] != 0.0) return fail(LLAMPC_E_ARG, "theta[0] must be 0");
+  for (int32_t i = 1; i < n; ++i)
+    if (!std::isfinite(theta[i]) || !(theta[i] > theta[i - 1]))
+      return fail(LLAMPC_E_ARG, "theta must be finite and strictly increasing (entry %d)", i);
+  if (!(track_length > theta[n - 1])) return fail(LLAMPC_E_ARG, "track_length must exceed theta[n-1]");
+  // the tangent's points lie 2 kTangentEps apart: a shorter lap would meet itself
+  if (!(track_length > 4 * kTangentEps)) return fail(LLAMPC_E_ARG, "track_length must exceed %g", 4 * kTangentEps);
+  if (!(track_width > 0)) return fail(LLAMPC_E_ARG, "track_width must be > 0");
+  std::lock_guard<std::mutex> lp(p->mu);
+  llampc_bank* b = p->b;
+  std::lock_guard<std::mutex> lk(b->mu);
+  bank_disarm(b);
+  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
+  DeviceGuard g(b->device);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // no launch reads the tables being replaced
+  p->tr_n = 0;
+  if (int rc = p->d_track.reserve(3 * (size_t)n, 0, "track tables")) return rc;
+  std::vector<double> h(3 * (size_t)n);
+  std::memcpy(h.data(), centre, 2 * (size_t)n * sizeof(double));
+  std::memcpy(h.data() + 2 * (size_t)n, theta, (size_t)n * sizeof(double));
+  HIP_TRY(hipMemcpy(p->d_track.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  p->tr_n = n;
+  p->tr_L = track_length;
+  p->tr_width = track_width;
+  return LLAMPC_OK;
+}
+
 }  // extern "C"
 
-// One solve: the unconstrained search (hp null: llampc_nlp_solve) or the corridor's (hp [H][6]
-// and its weight, checked by the caller: llampc_nlp_solve_corridor).
+// What the device corridor needs before anything is launched (the caller holds p->mu): a track, a
+// finite path [2][H+1] and a margin that leaves a corridor.
+static int track_corridor_args(const llampc_nlp* p, const double* path, double margin) {
+  if (!p->tr_n) return fail(LLAMPC_E_STATE, "no track set: call llampc_nlp_set_track first");
+  for (int i = 0; i < 2 * (p->cfg.H + 1); ++i)
+    if (!std::isfinite(path[i])) return fail(LLAMPC_E_ARG, "path: entry %d is not finite", i);
+  if (!std::isfinite(margin) || !(p->tr_width / 2 - margin > 0))
+    return fail(LLAMPC_E_ARG, "margin %g leaves no corridor (track width %g)", margin, p->tr_width);
+  return LLAMPC_OK;
+}
+
+// Enqueues track_corridor_kernel on s: the half-planes along `path` into the solver's pinned
+// buffer (hp [H][6], then theta [H] from 6 HMAX on), which starts as NaN so that a row the kernel
+// did not write fails corridor_invalid afterwards.
+static int enqueue_track_corridor(llampc_nlp* p, const double* path, double margin, hipStream_t s) {
+  const int H = p->cfg.H;
+  const size_t n = (size_t)p->tr_n;
+  CorridorPath cp{};
+  std::memcpy(cp.v, path, 2 * (size_t)(H + 1) * sizeof(double));
+  for (int i = 0; i < 6 * H; ++i) p->hp.get()[i] = __builtin_nan("");
+  for (int i = 0; i < H; ++i) p->hp.get()[6 * LLAMPC_HMAX + i] = __builtin_nan("");
+  const double* d = p->d_track.get();
+  const TrackK t{d, d + n, d + 2 * n, p->tr_n, 0, p->tr_L};
+  TimedLaunch tl(p->b, 1, s);              // llampc_bank_timing's kernel 1: the corridor kernel alone
+  HIP_TRY(launch_track_corridor(t, cp, H, p->tr_width / 2 - margin, p->hp.dev(), p->hp.dev() + 6 * LLAMPC_HMAX, s));
+  p->b->launches++;
+  return LLAMPC_OK;
+}
+
+// One solve: the unconstrained search (hp and path null: llampc_nlp_solve), the corridor's with the
+// caller's half-planes (hp [H][6] and the weight, checked by the caller: llampc_nlp_solve_corridor)
+// or with the track's along `path` [2][H+1], built on the device ahead of the search
+// (llampc_nlp_solve_track; hp_out [H][6] or null: what the kernel built).
 static int nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const double* uprev, const double* base,
                      int32_t has_hold, const double* hp, double weight, double* umpc, double* fval, double* xmpc,
-                     double* max_slack) {
+                     double* max_slack, const double* path = nullptr, double margin = 0.0, double* hp_out = nullptr) {
   std::lock_guard<std::mutex> lp(p->mu);
   llampc_bank* b = p->b;
   std::lock_guard<std::mutex> lk(b->mu);
@@ -100,15 +174,20 @@ static int nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
   const int H = k.H;
   hipStream_t s = b->stream;
   NlpCorridor cor{};
-  if (hp) {
+  const bool corridor = hp || path;
+  if (corridor) {
     if (nlp_corridor_lds_bytes(H, k.samples, k.elite) > 160 * 1024)
       return fail(LLAMPC_E_ARG, "H x elite too large for LDS with a corridor");
-    std::memcpy(p->hp.get(), hp, 6 * (size_t)H * sizeof(double));
     cor.hp = p->hp.dev();
     cor.weight = weight;
   }
+  if (hp) std::memcpy(p->hp.get(), hp, 6 * (size_t)H * sizeof(double));
+  if (path) {
+    if (int rc = track_corridor_args(p, path, margin)) return rc;
+    if (int rc = enqueue_track_corridor(p, path, margin, s)) return rc;
+  }
   auto launch = [&](const NlpLaunch& a, const NlpInline& pk) {
-    return hp ? launch_nlp_corridor(a, pk, cor, s) : launch_nlp(a, pk, s);
+    return corridor ? launch_nlp_corridor(a, pk, cor, s) : launch_nlp(a, pk, s);
   };
   // the launch's inputs (NlpInline): x0, xref, the first mean (base or uprev held); the first
   // std is sigma0, the best so far starts at +inf (the kernel's round 0)
@@ -134,7 +213,7 @@ static int nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
   a.host_tag = p->host.tag.dev();
   a.host_seq = p->calls + 1;
   a.ms_tag = p->d_ms_tag.get();
-  a.ltraj = hp ? p->ltraj_cor : p->ltraj;
+  a.ltraj = corridor ? p->ltraj_cor : p->ltraj;
   a.seed = k.seed;
   a.call = p->calls;
   a.up0 = uprev[0];
@@ -190,6 +269,15 @@ static int nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
   if (fval) *fval = r->best_j;
   if (xmpc) std::memcpy(xmpc, &r->traj[0][0], 6 * (size_t)(H + 1) * sizeof(double));
   if (hp && max_slack) *max_slack = corridor_max_slack(hp, &r->traj[0][0], H);
+  if (path) {
+    // the corridor kernel ended before the search began, whose completion tag has arrived
+    double built[6 * LLAMPC_HMAX];
+    std::memcpy(built, p->hp.get(), 6 * (size_t)H * sizeof(double));
+    if (hp_out) std::memcpy(hp_out, built, 6 * (size_t)H * sizeof(double));
+    if (const char* why = corridor_invalid(built, H, weight))
+      return fail(LLAMPC_E_DEVICE, "the device-built corridor: %s", why);
+    if (max_slack) *max_slack = corridor_max_slack(built, &r->traj[0][0], H);
+  }
   if (r->best_it < 0) return fail(LLAMPC_E_DEVICE, "no finite objective in %d rounds of %d samples", k.iters, k.samples);
   return LLAMPC_OK;
 }
@@ -209,6 +297,34 @@ int llampc_nlp_solve_corridor(llampc_nlp* p, const double* x0, const double* xre
   if (!hp) return fail(LLAMPC_E_ARG, "hp is NULL (llampc_nlp_solve is the unconstrained solve)");
   if (const char* why = corridor_invalid(hp, p->cfg.H, weight)) return fail(LLAMPC_E_ARG, "corridor: %s", why);
   return nlp_solve(p, x0, xref, uprev, base, has_hold, hp, weight, umpc, fval, xmpc, max_slack);
+}
+
+int llampc_nlp_solve_track(llampc_nlp* p, const double* x0, const double* xref, const double* uprev,
+                           const double* base, int32_t has_hold, const double* path, double margin, double weight,
+                           double* umpc, double* fval, double* xmpc, double* max_slack, double* hp_out) {
+  if (!p || !x0 || !xref || !uprev || !umpc) return fail(LLAMPC_E_ARG, "NULL argument");
+  if (!path) return fail(LLAMPC_E_ARG, "path is NULL");
+  if (!(weight >= 0) || !std::isfinite(weight)) return fail(LLAMPC_E_ARG, "corridor: weight must be finite and >= 0");
+  return nlp_solve(p, x0, xref, uprev, base, has_hold, nullptr, weight, umpc, fval, xmpc, max_slack, path, margin,
+                   hp_out);
+}
+
+int llampc_nlp_track_corridor(llampc_nlp* p, const double* path, double margin, double* hp, double* theta) {
+  if (!p || !path || !hp) return fail(LLAMPC_E_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lp(p->mu);
+  llampc_bank* b = p->b;
+  std::lock_guard<std::mutex> lk(b->mu);
+  bank_disarm(b);
+  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
+  DeviceGuard g(b->device);
+  const int H = p->cfg.H;
+  if (int rc = track_corridor_args(p, path, margin)) return rc;
+  if (int rc = enqueue_track_corridor(p, path, margin, b->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  std::memcpy(hp, p->hp.get(), 6 * (size_t)H * sizeof(double));
+  if (theta) std::memcpy(theta, p->hp.get() + 6 * LLAMPC_HMAX, (size_t)H * sizeof(double));
+  if (const char* why = corridor_invalid(hp, H, 0.0)) return fail(LLAMPC_E_DEVICE, "the device-built corridor: %s", why);
+  return LLAMPC_OK;
 }
 
 }  // extern "C"

@@ -13,6 +13,8 @@
 //   merge_kernel       cross-shard merge after the RCCL all-gather (merge.hpp).
 //   dynamics_kernel / integrate_kernel   raw batched Dynamic API (dynamic.py:98-154,
 //                      model.py:18-40, rk6.py).
+//   track_corridor_kernel   one block per horizon step: the track's half-planes along a path
+//                      (corridor_dev.hpp; constraints.track_corridor on the device).
 //
 // This translation unit: the plan-launch dispatcher (launch_plan) and the non-plan kernels.
 // The plan kernels are in plan_dev.hpp (their device code in the *_dev.hpp role headers), their
@@ -154,6 +156,80 @@ __global__ __launch_bounds__(kBlock) void math_kernel(int32_t fn, const double* 
     default: r = __builtin_nan("");
   }
   out[i] = r;
+}
+
+// The track corridor along a path (corridor_dev.hpp; llampc_nlp_track_corridor and, ahead of the
+// corridor solve on the same stream, llampc_nlp_solve_track).  One block per step k = 1..H.  The
+// block first copies the track's three tables into its LDS (24 n bytes, 16 KB on ETHZ: independent
+// loads, one memory round trip), and everything after reads them there — with the tables in global
+// memory the bisection's ten dependent loads alone, cold in the block's L2, made the kernel 8.8 us
+// long (DESIGN §3 "The corridor").  Each thread takes the segments j = tid (mod 256) in ascending
+// order, the (d2, j) pairs are reduced over the wave (DPP) and over the four waves (LDS) with ties
+// to the lower j; wave 0 then looks up the centre and the tangent's two points in lanes 0, 1, 2 and
+// lane 0 stores row k - 1 and theta_k with plain vector stores.  No block waits on anything.  hp
+// is the device alias of pinned host memory in both callers: the system-scope fence orders the row
+// before the kernel's end.  Dynamic LDS: sv [4] | si [4] | cx [n] | cy [n] | tt [n].
+constexpr size_t kCorridorScratch = 64;
+__global__ __launch_bounds__(kBlock) void track_corridor_kernel(TrackK g, CorridorPath path, int32_t H, double hw,
+                                                                double* hp, double* theta_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* sv = reinterpret_cast<double*>(smem);
+  int64_t* si = reinterpret_cast<int64_t*>(smem + 32);
+  double* lx = reinterpret_cast<double*>(smem + kCorridorScratch);
+  double* ly = lx + g.n;
+  double* lt = ly + g.n;
+  const int tid = threadIdx.x;
+  const int k = blockIdx.x + 1;
+  const double px = path.v[k], py = path.v[H + 1 + k];
+#pragma unroll 4
+  for (int j = tid; j < g.n; j += kBlock) {
+    lx[j] = g.cx[j];
+    ly[j] = g.cy[j];
+    lt[j] = g.tt[j];
+  }
+  __syncthreads();
+  const TrackK t{lx, ly, lt, g.n, 0, g.L};
+  // a lane with no segment holds (NaN, kNoIndex): last under the NaN-last order
+  double bd2 = __builtin_nan("");
+  int64_t bj = kNoIndex;
+  for (int j = tid; j < t.n; j += kBlock) {
+    const double d2 = corridor_seg_d2(t, j, px, py);
+    if (bj == kNoIndex || d2 < bd2) {
+      bd2 = d2;
+      bj = j;
+    }
+  }
+  wave_min<0>(bd2, bj);
+  if ((tid & 63) == 0) {
+    sv[tid >> 6] = bd2;
+    si[tid >> 6] = bj;
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  bd2 = sv[0];
+  bj = si[0];
+#pragma unroll
+  for (int w = 1; w < kBlock / 64; ++w) {
+    if (less_nan_last(sv[w], si[w], bd2, bj)) {
+      bd2 = sv[w];
+      bj = si[w];
+    }
+  }
+  const int j = (int)(bj < 0 ? 0 : (bj > t.n - 1 ? t.n - 1 : bj));   // inside the tables whatever the path
+  const double theta = corridor_theta(t, j, px, py);
+  double x, y;
+  corridor_param_to_xy(t, corridor_lookup_theta(theta, t.L, tid < 3 ? tid : 0), x, y);
+  const double fx = readlane_d(x, 1), fy = readlane_d(y, 1);
+  const double bx = readlane_d(x, 2), by = readlane_d(y, 2);
+  if (tid == 0) {
+    double row[6];
+    corridor_row(x, y, fx, fy, bx, by, hw, row);
+    double* out = hp + 6 * (size_t)(k - 1);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) out[i] = row[i];
+    if (theta_out) theta_out[k - 1] = theta;
+    __threadfence_system();
+  }
 }
 
 template <int INTEG>
@@ -409,6 +485,16 @@ hipError_t launch_peer_exchange(const PeerLaunch& a, hipStream_t s) {
                      (kBlock / 64) * sizeof(int);
   allow_lds(peer_exchange_kernel);
   hipLaunchKernelGGL(peer_exchange_kernel, dim3(1), dim3(kBlock), lds, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_track_corridor(const TrackK& t, const CorridorPath& path, int32_t H, double hw, double* hp,
+                                 double* theta, hipStream_t s) {
+  if (H < 1 || H > LLAMPC_HMAX || t.n < 2 || t.n > kTrackMaxPoints || !t.cx || !t.cy || !t.tt || !hp)
+    return hipErrorInvalidValue;
+  allow_lds(track_corridor_kernel);      // 96 KB of tables at the largest centre line
+  hipLaunchKernelGGL(track_corridor_kernel, dim3(H), dim3(kBlock), kCorridorScratch + 24 * (size_t)t.n, s, t, path, H,
+                     hw, hp, theta);
   return hipGetLastError();
 }
 

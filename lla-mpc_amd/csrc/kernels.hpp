@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "corridor_dev.hpp"
 #include "dyn.hpp"
 #include "raceline.hpp"
 #include "llampc.h"
@@ -189,6 +190,14 @@ struct PeerLaunch {
 hipError_t launch_peer_exchange(const PeerLaunch& a, hipStream_t s);
 // Largest world the plan launch can merge in its own LDS (records + lists, see launch_plan).
 constexpr int kPeerFuseMax = 16;
+// The track corridor along a path (track_corridor_kernel; corridor_dev.hpp): one block per step
+// k = 1..H writes row k - 1 of hp [H][6] and theta [H] (or null).  The path [2][H+1] travels in the
+// kernarg segment, as the solve's inputs do (NlpInline): no host-to-device copy.
+struct CorridorPath {
+  double v[2 * (LLAMPC_HMAX + 1)];
+};
+hipError_t launch_track_corridor(const TrackK& t, const CorridorPath& path, int32_t H, double hw, double* hp,
+                                 double* theta, hipStream_t s);
 hipError_t launch_dynamics(int32_t op, const double* x, const double* u, const double* params,
                            int64_t P, VehK veh, int64_t n, double* out, hipStream_t s);
 hipError_t launch_math(int32_t fn, const double* a, const double* b, int64_t n, double* out,

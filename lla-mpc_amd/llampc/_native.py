@@ -172,6 +172,14 @@ _SIGNATURES = {
     # ... hp [H][6], weight, then umpc, fval, xmpc, max_slack
     "llampc_nlp_solve_corridor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # centre [2][n], theta [n], n, track_length, track_width
+    "llampc_nlp_set_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double]),
+    # path [2][H+1], margin -> hp [H][6], theta [H] (or NULL)
+    "llampc_nlp_track_corridor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    # llampc_nlp_solve_corridor's, with path [2][H+1], margin in hp's place and hp_out [H][6] last
+    "llampc_nlp_solve_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     "llampc_nlp_destroy": (C.c_int, [C.c_void_p]),
     "llampc_dynamics_batch": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.POINTER(Vehicle), C.c_int64, C.c_void_p, C.c_int32,

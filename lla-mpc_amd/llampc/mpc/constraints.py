@@ -7,6 +7,9 @@ slacks max(a.p_k - b, 0)^2 + max(c.p_k - d, 0)^2 (csrc/rollout_dev.hpp corridor_
 
 ``track_corridor`` builds the corridor of a packaged track around a reference, ``strip`` one
 around any polyline; ``slacks`` evaluates a trajectory on a corridor in the device's order.
+``setupNLP(device_corridor=True)`` builds ``track_corridor``'s half-planes on the device instead
+(csrc/corridor_dev.hpp restates the function in scalar form, equal to it to 1e-12) along
+``default_path`` or the caller's own path.
 
 The reference's constraints.py (``Boundary()``: the boundary lines linearised per step, with
 slack variables in the NLP) is not restated here; this is the same geometry — two parallel
@@ -56,6 +59,32 @@ def track_corridor(track, xref, margin=0.0):
         n = _left_normal(fwd - back)
         hp[k - 1] = _record(n, float(n @ c), hw)
     return hp
+
+
+def default_path(x0, H, Ts, prev_xmpc=None):
+    """The path [2, H+1] a ``setupNLP(device_corridor=True)`` solve builds its corridor along when
+    the caller gives none.  With the previous solve's ``prev_xmpc`` ([6, H+1], or its first two
+    rows): its positions shifted one step, the last one repeated — the warm start's rule, so the
+    corridor follows where the search starts.  Without (the first solve): the ray from the car,
+    P_k = (X0, Y0) + k Ts max(vx0, 0.05) (cos psi0, sin psi0), 0.05 the NLP's own vmin.  (Not
+    ``xref``: ConstantSpeed runs far ahead of the car on the recorded states, and the corridor
+    along it leaves the unconstrained optimum 0.2-0.9 m outside the walls.)  At a long horizon
+    with a spinning car the ray leaves the track: a caller who knows better passes
+    ``corridor_path``."""
+    H = int(H)
+    out = np.empty((2, H + 1))
+    if prev_xmpc is not None:
+        P = np.asarray(prev_xmpc, dtype=np.float64)
+        if P.ndim != 2 or P.shape[0] < 2 or P.shape[1] != H + 1:
+            raise ValueError(f"prev_xmpc must be [6, H+1] = {(6, H + 1)}, got {P.shape}")
+        out[:, :-1] = P[:2, 1:]
+        out[:, -1] = P[:2, -1]
+        return out
+    x0 = np.asarray(x0, dtype=np.float64).ravel()
+    step = np.arange(H + 1) * (float(Ts) * max(float(x0[3]), 0.05))
+    out[0] = x0[0] + step * np.cos(x0[2])
+    out[1] = x0[1] + step * np.sin(x0[2])
+    return out
 
 
 def strip(path, half, offset=0.0):

@@ -34,6 +34,17 @@ return value is ``Ts`` if the largest slack along ``xmpc`` (``self.max_slack``) 
 corridors: ``track_corridor(track, xref)`` from a track's centre line and width, ``strip`` around
 any polyline.  ``corridor=None`` is the unconstrained solve, unchanged.
 
+``setupNLP(..., device_corridor=True, corridor_margin=m)`` builds the track's corridor on the
+device instead (llampc_nlp_solve_track: a small kernel ahead of the search on the same stream,
+csrc/corridor_dev.hpp — ``track_corridor`` in scalar form, equal to it to 1e-12; the host
+function's Python loop costs milliseconds per tick).  The track's centre line, arc lengths, length
+and width are uploaded once; a solve without ``corridor=`` then takes the corridor along
+``corridor_path`` [2, H+1] if given, else along ``constraints.default_path``: the previous solve's
+positions shifted one step, or on the first solve the ray from the car (which leaves the track at
+a long horizon with a spinning car: pass ``corridor_path`` then).  ``last_corridor`` is a copy of
+the half-planes the device built; ``max_slack`` and the violation flag are as for ``corridor=``,
+which still wins when given.  ``track_corridor(path)`` is the device builder alone.
+
 ``track_cons=True`` (rt.py:63 uses False everywhere) would add the track-boundary half-planes
 of constraints.py with the reference's own linearisation and slack variables, which cannot be
 restated here (constraints.py is not available): it raises, and points to
@@ -44,6 +55,7 @@ from __future__ import annotations
 import numpy as np
 
 from llampc import _native as nat
+from llampc.mpc import constraints
 from llampc.mpc.bank import ModelBank, SHARED_KEYS
 
 _PACEJKA = ("Bf", "Cf", "Df", "Br", "Cr", "Dr")
@@ -60,7 +72,7 @@ class setupNLP:
 
     def __init__(self, horizon, Ts, Q, P, R, params, model, track, track_cons=False,
                  samples=1024, iters=8, elite=32, sigma=(0.3, 0.15), std_floor=1e-4, seed=0, device=0,
-                 corridor_weight=1e4, corridor_tol=1e-4):
+                 corridor_weight=1e4, corridor_tol=1e-4, device_corridor=False, corridor_margin=0.0):
         if track_cons:
             raise NotImplementedError("track_cons=True (constraints.py boundary half-planes) is not "
                                       "implemented: the reference's LLA-MPC runs use TRACK_CONS=False (rt.py:63); "
@@ -70,6 +82,18 @@ class setupNLP:
         if not (np.isfinite(self.corridor_weight) and self.corridor_weight >= 0):
             raise ValueError("corridor_weight must be finite and >= 0")
         self.max_slack = 0.0         # the last corridor solve's largest slack along xmpc
+        self.device_corridor, self.corridor_margin = bool(device_corridor), float(corridor_margin)
+        if self.device_corridor:
+            missing = [k for k in ("center_line", "theta_track", "track_length", "track_width")
+                       if getattr(track, k, None) is None]
+            if track is None or missing:
+                raise ValueError("device_corridor=True needs a track with center_line, theta_track, track_length "
+                                 f"and track_width (missing: {'the track' if track is None else ', '.join(missing)})")
+            if not self.corridor_margin < float(track.track_width) / 2:      # a NaN margin too
+                raise ValueError(f"corridor_margin {corridor_margin} leaves no corridor "
+                                 f"(track width {track.track_width})")
+        self.last_corridor = None    # the last device-built corridor [H, 6]
+        self._last_xmpc = None       # the last solve's positions [2, H+1] (constraints.default_path)
         self.horizon, self.Ts = int(horizon), float(Ts)
         self.params, self.model, self.track, self.track_cons = params, model, track, track_cons
         self.samples, self.iters, self.elite = int(samples), int(iters), int(elite)
@@ -121,17 +145,56 @@ class setupNLP:
         H = self.horizon
         self._io = {"x0": np.zeros(6), "xref": np.zeros((2, H + 1)), "up": np.zeros(2), "base": np.zeros((H, 2)),
                     "umpc": np.zeros((H, 2)), "fval": np.zeros(1), "xmpc": np.zeros((H + 1, 6)),
-                    "hp": np.zeros((H, 6)), "slack": np.zeros(1)}
+                    "hp": np.zeros((H, 6)), "slack": np.zeros(1), "path": np.zeros((2, H + 1)),
+                    "theta": np.zeros(H)}
         self._addr = {k: v.ctypes.data for k, v in self._io.items()}
+        if self.device_corridor:
+            tr = self.track
+            centre = np.ascontiguousarray(tr.center_line, dtype=np.float64)
+            theta = np.ascontiguousarray(tr.theta_track, dtype=np.float64)
+            if centre.ndim != 2 or centre.shape[0] != 2 or theta.shape != (centre.shape[1],):
+                raise ValueError(f"track: center_line {centre.shape} and theta_track {theta.shape} must be "
+                                 "[2, n] and [n]")
+            nat.check(nat.load().llampc_nlp_set_track(h, centre.ctypes.data, theta.ctypes.data, centre.shape[1],
+                                                      float(tr.track_length), float(tr.track_width)))
 
-    def solve(self, x0, xref, uprev, corridor=None):
+    def _path(self, path):
+        """A corridor path as the library takes it: [2, H+1], finite (checked before the library)."""
+        path = np.asarray(path, dtype=np.float64)
+        if path.shape != (2, self.horizon + 1):
+            raise ValueError(f"corridor_path must be [2, H+1] = {(2, self.horizon + 1)}, got {path.shape}")
+        if not np.all(np.isfinite(path)):
+            raise ValueError("corridor_path must be finite")
+        return path
+
+    def track_corridor(self, path, margin=None):
+        """The track's corridor along ``path`` [2, H+1] built on the device
+        (llampc_nlp_track_corridor): -> (hp [H, 6], theta [H]), constraints.track_corridor(track,
+        path, margin) and track.xy_to_param of the path's points to 1e-12.  margin: None =
+        corridor_margin.  Needs device_corridor=True."""
+        if not self.device_corridor:
+            raise ValueError("track_corridor needs setupNLP(..., device_corridor=True)")
+        path = self._path(path)
+        self._ensure()
+        b, a = self._io, self._addr
+        b["path"][:] = path
+        m = self.corridor_margin if margin is None else float(margin)
+        nat.check(nat.load().llampc_nlp_track_corridor(self._h, a["path"], m, a["hp"], a["theta"]))
+        return b["hp"].copy(), b["theta"].copy()
+
+    def solve(self, x0, xref, uprev, corridor=None, corridor_path=None):
         """-> (umpc [2, H], fval, xmpc [6, H+1], violation in {0, Ts}) as nmpc.py:161-203.
         corridor: None, or the half-planes [H, 6] (module doc); violation is then Ts if the largest
-        slack along xmpc exceeds corridor_tol."""
+        slack along xmpc exceeds corridor_tol.  With device_corridor=True and no corridor: the
+        track's corridor along corridor_path [2, H+1], or along constraints.default_path."""
         if corridor is not None:
             corridor = np.asarray(corridor, dtype=np.float64)
             if corridor.shape != (self.horizon, 6):
                 raise ValueError(f"corridor must be [H, 6] = {(self.horizon, 6)}, got {corridor.shape}")
+        elif corridor_path is not None:
+            if not self.device_corridor:
+                raise ValueError("corridor_path needs setupNLP(..., device_corridor=True)")
+            corridor_path = self._path(corridor_path)
         self._ensure()
         b = self._io
         H = self.horizon
@@ -146,7 +209,18 @@ class setupNLP:
             b["base"][-1] = self._last[-1]
         a = self._addr
         violation = 0.0
-        if corridor is None:
+        if corridor is None and self.device_corridor:
+            if corridor_path is None:
+                corridor_path = constraints.default_path(b["x0"], H, self.Ts, self._last_xmpc)
+            b["path"][:] = corridor_path
+            nat.check(nat.load().llampc_nlp_solve_track(self._h, a["x0"], a["xref"], a["up"],
+                                                         a["base"] if hold else None, int(hold), a["path"],
+                                                         self.corridor_margin, self.corridor_weight, a["umpc"],
+                                                         a["fval"], a["xmpc"], a["slack"], a["hp"]))
+            self.last_corridor = b["hp"].copy()
+            self.max_slack = float(b["slack"][0])
+            violation = self.Ts if self.max_slack > self.corridor_tol else 0.0
+        elif corridor is None:
             nat.check(nat.load().llampc_nlp_solve(self._h, a["x0"], a["xref"], a["up"], a["base"] if hold else None,
                                                    int(hold), a["umpc"], a["fval"], a["xmpc"]))
         else:
@@ -159,7 +233,10 @@ class setupNLP:
             violation = self.Ts if self.max_slack > self.corridor_tol else 0.0
         umpc = b["umpc"].copy()
         self._last = umpc
-        return umpc.T.copy(), float(b["fval"][0]), b["xmpc"].T.copy(), violation
+        xmpc = b["xmpc"].T.copy()
+        if self.device_corridor:
+            self._last_xmpc = xmpc[:2].copy()
+        return umpc.T.copy(), float(b["fval"][0]), xmpc, violation
 
     def close(self):
         if self._h is not None:
