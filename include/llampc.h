@@ -23,6 +23,9 @@
  *  llampc_exchange_rccl / _peer    (new) the per-tick gather + merge of the sharded bank
  *                                  (SURVEY.md §8e): RCCL all-gather, or xGMI mailboxes
  *  llampc_nlp_*                    setupNLP / .solve (nmpc.py:14-203), solved by sampling
+ *  llampc_nlp_batch_*              (new) the per-model setupNLP bank and the solve with the
+ *                                  selected one (rt.py:195-202, 305): B problems of a model
+ *                                  bank, by model index, in one launch
  *  llampc_dynamics_batch           Dynamic.calc_forces_batch (llampc/models/dynamic.py:
  *                                  117-154), Dynamic._diffequation_batch (:98-115)
  *  llampc_ctl_*                    the control loop body rt.py:278-366 on the device
@@ -528,6 +531,43 @@ int llampc_nlp_solve_track(llampc_nlp* nlp, const double* x0, const double* xref
                            double margin, double weight, double* umpc, double* fval, double* xmpc,
                            double* max_slack, double* hp_out /* [H][6], may be NULL */);
 int llampc_nlp_destroy(llampc_nlp* nlp);
+
+/* ---- batched setupNLP.solve: B problems of a model bank in one launch ---------------- */
+/* The reference builds one setupNLP per bank model (rt.py:195-202) and solves each tick with the
+ * model the look-back selected (rt.py:305).  One solver handle per model does not scale to a bank
+ * of 10^4; this solver is bound to the whole bank (any n >= 1, borrowed: destroy the solver first)
+ * and solves B independent problems per call in ONE launch, each with its own bank model (by
+ * index: e.g. llampc_plan_out.sel_model and topk), state, reference, previous input, warm start
+ * and Philox seed, each on its own samples / 64 blocks (csrc/nlp_batch.hip).  The vehicle
+ * constants are the bank's, the cost, bounds, rates and shape the cfg's, shared by the batch.
+ * A problem's search is llampc_nlp_solve's, bit for bit: problem p of the handle's c-th call
+ * (c = 0, 1, ..: one solve number per call, the Philox call word of every problem of it) draws
+ * the noise of the c-th call of a single solver created with seed[p].
+ * The problems' blocks wait for each other's rounds, so max_batch x samples / 64 must not exceed
+ * the device's CU count (LLAMPC_E_ARG at create), and a batch of B holds B x samples / 64 CUs
+ * for the solve's duration.  The cfg checks are llampc_nlp_create's. */
+typedef struct llampc_nlp_batch llampc_nlp_batch;
+int llampc_nlp_batch_create(llampc_bank* bank, const llampc_nlp_cfg* cfg, int32_t max_batch,
+                            llampc_nlp_batch** out);
+/* -> max_batch and the CU count read at the bank's create (either may be NULL). */
+int llampc_nlp_batch_info(const llampc_nlp_batch* nb, int32_t* max_batch, int32_t* cus);
+/* status[p] of a problem */
+enum llampc_nlp_status { LLAMPC_NLP_OK = 0,
+                         LLAMPC_NLP_NO_FINITE = 1,   /* no finite objective in any round         */
+                         LLAMPC_NLP_NO_TAG = 2 };    /* its completion tag never arrived          */
+/* model_idx [B] in [0, n); seed [B] or NULL (= cfg.seed for all); x0 [B][6]; xref [B][2][H+1];
+ * uprev [B][2]; base [B][H][2] or NULL (every first mean = uprev held; a problem whose has_hold
+ * is 0 ignores its row of base and holds uprev too, so warm and cold slots mix in one call);
+ * has_hold [B] -> umpc [B][H][2], fval [B], xmpc [B][H+1][6], status [B].  The host writes the
+ * inputs into a pinned mapped buffer, launches once and waits for the B completion tags with one
+ * bounded wait.  Returns LLAMPC_OK when every problem reported: a problem's failure is its
+ * status, with umpc zeros and fval +inf, and stops no other problem.  LLAMPC_E_ARG, with nothing
+ * launched and the bank's launch counter unchanged: a NULL pointer (seed and base excepted),
+ * B < 1 or B > max_batch, a model index outside [0, n).  Blocking. */
+int llampc_nlp_batch_solve(llampc_nlp_batch* nb, int32_t B, const int64_t* model_idx, const uint64_t* seed,
+                           const double* x0, const double* xref, const double* uprev, const double* base,
+                           const int32_t* has_hold, double* umpc, double* fval, double* xmpc, int32_t* status);
+int llampc_nlp_batch_destroy(llampc_nlp_batch* nb);
 
 /* ---- raw batched dynamics (Dynamic API parity) ---------------------------------- */
 /* x [n][6], u [n][2]; params [6][P] with P == 1 (one model broadcast) or P == n.

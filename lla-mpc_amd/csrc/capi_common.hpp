@@ -1,6 +1,6 @@
 // capi_common.hpp — what the C ABI's translation units share (capi.hip: errors, bank, plan and
 // batch calls; capi_xchg.hip: RCCL, mailboxes, exchange; capi_ctl.hip: the controller;
-// capi_nlp.hip: the NLP solver): error reporting, the owners of device and pinned memory, the
+// capi_nlp.hip: the NLP solver; capi_nlp_batch.hip: the batched NLP solver): error reporting, the owners of device and pinned memory, the
 // handle structs and the few functions one file calls in another.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -218,6 +218,9 @@ int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out
                 const llampc::InlinePack* pk = nullptr, llampc_mailbox* px = nullptr,
                 llampc_plan_out* px_merged = nullptr);
 inline hipStream_t pick_stream(llampc_bank* b, void* s) { return s ? (hipStream_t)s : b->stream; }
+
+// llampc_nlp_create's checks of a cfg (capi_nlp.hip), llampc_nlp_batch_create's too.
+int nlp_check_cfg(const llampc_nlp_cfg& k);
 
 // Event pair around a GROUP of timing_stride consecutive launches of kernel `k` (0 the plan
 // kernel; 1, 2 reserved): start before the group's first launch, stop after its last, so a

@@ -94,6 +94,104 @@ inline double corridor_max_slack(const double* hp, const double* xmpc, int32_t H
   return m;
 }
 
+// What a launch of the NLP search takes from the solver's cfg and its bank (params [6][n], the
+// vehicle), the same for every solve of a solver and every problem of a batch.
+inline void nlp_launch_cfg(NlpLaunch& a, const llampc_nlp_cfg& k, const VehK& veh, const double* params, int64_t n) {
+  a.la.params = params;
+  a.la.n = n;
+  a.la.veh = integrator_veh(veh, LLAMPC_EULER_NLP);
+  a.la.C = 64;
+  a.la.H = k.H;
+  a.la.integrator = LLAMPC_EULER_NLP;
+  a.la.Ts = k.Ts;
+  a.la.cost = make_cost(k.cost, k.Ts);
+  a.umin0 = k.cost.umin[0];
+  a.umin1 = k.cost.umin[1];
+  a.umax0 = k.cost.umax[0];
+  a.umax1 = k.cost.umax[1];
+  a.rlo0 = k.rate_lo[0];
+  a.rlo1 = k.rate_lo[1];
+  a.rhi0 = k.rate_hi[0];
+  a.rhi1 = k.rate_hi[1];
+  a.std_floor = k.std_floor;
+  a.sig0 = k.sigma0[0];
+  a.sig1 = k.sigma0[1];
+  a.H = k.H;
+  a.samples = k.samples;
+  a.elite = k.elite;
+  a.iters = k.iters;                    // the last round's completion writes xmpc (nmpc.py:58-60)
+}
+
+// The batched NLP solve's buffers (llampc_nlp_batch_*; nlp.hpp NlpBatch): per problem one input
+// record in the pinned mapped buffer, 64-bit words x0 [6] | xref [2][H+1] | the first mean [H][2] |
+// uprev [2] at up_off | the Philox seed | model index (low half), has_hold (high), padded to whole
+// 64-byte lines so that no two problems share one; one region of tagged list words [2][3][samples],
+// of candidate rows [2][samples][H][2], of mean / std words [2][4 HMAX]; one NlpState, one
+// NlpResult and one line of host-tag words.  Problem p's part of each starts p strides in.
+struct NlpBatchLayout {
+  size_t rec_words, up_off;              // the record's stride and its uprev offset, in words
+  size_t list_words, cand_doubles, ms_words, tag_words;
+};
+inline NlpBatchLayout nlp_batch_layout(int32_t H, int32_t samples) {
+  NlpBatchLayout l;
+  l.up_off = 6 + 2 * ((size_t)H + 1) + 2 * (size_t)H;
+  l.rec_words = (l.up_off + 4 + 7) / 8 * 8;
+  l.list_words = 6 * (size_t)samples;
+  l.cand_doubles = 4 * (size_t)samples * (size_t)H;
+  l.ms_words = 8 * (size_t)LLAMPC_HMAX;
+  l.tag_words = 8;
+  return l;
+}
+inline NlpBatch nlp_batch_arg(const NlpBatchLayout& l, const uint64_t* in, int32_t samples) {
+  NlpBatch b{};
+  b.in = in;
+  b.cand_doubles = l.cand_doubles;
+  b.rec_words = (uint32_t)l.rec_words;
+  b.up_off = (uint32_t)l.up_off;
+  b.list_words = (uint32_t)l.list_words;
+  b.ms_words = (uint32_t)l.ms_words;
+  b.tag_words = (uint32_t)l.tag_words;
+  for (int nl = samples / 64; nl > 1; nl >>= 1) b.nl_log2++;
+  return b;
+}
+
+// One problem's record (rec_words words at `rec`): base [H][2] or null = uprev held.
+inline void nlp_batch_pack(const NlpBatchLayout& l, int32_t H, uint64_t* rec, const double* x0, const double* xref,
+                           const double* uprev, const double* base, uint64_t seed, int64_t model, int32_t has_hold) {
+  double* d = reinterpret_cast<double*>(rec);
+  std::memcpy(d, x0, 6 * sizeof(double));
+  std::memcpy(d + 6, xref, 2 * ((size_t)H + 1) * sizeof(double));
+  double* m0 = d + 6 + 2 * ((size_t)H + 1);
+  for (int i = 0; i < H; ++i)
+    for (int j = 0; j < 2; ++j) m0[2 * i + j] = base ? base[2 * i + j] : uprev[j];
+  d[l.up_off] = uprev[0];
+  d[l.up_off + 1] = uprev[1];
+  rec[l.up_off + 2] = seed;
+  rec[l.up_off + 3] = (uint64_t)(uint32_t)model | ((uint64_t)(uint32_t)has_hold << 32);
+}
+
+// What llampc_nlp_batch_create refuses beyond llampc_nlp_create's cfg checks: null if valid.  The
+// problems' blocks wait for each other's rounds, so all of a full batch's must be resident at once
+// (one block per CU by its LDS request).
+inline const char* nlp_batch_create_invalid(int64_t n, int32_t samples, int32_t max_batch, int32_t cus) {
+  if (n < 1) return "the bank holds no model";
+  if (n > 0xFFFFFFFFll) return "the bank holds more models than a record's index word";
+  if (max_batch < 1) return "max_batch must be >= 1";
+  if ((int64_t)max_batch * (samples / 64) > cus) return "max_batch x samples / 64 blocks exceed the device's CUs";
+  return nullptr;
+}
+
+// What llampc_nlp_batch_solve refuses before anything is written or launched: null if valid.
+inline const char* nlp_batch_args_invalid(int32_t B, int32_t max_batch, const int64_t* model_idx, int64_t n,
+                                          const void* x0, const void* xref, const void* uprev, const void* has_hold,
+                                          const void* umpc, const void* fval, const void* xmpc, const void* status) {
+  if (!model_idx || !x0 || !xref || !uprev || !has_hold || !umpc || !fval || !xmpc || !status) return "NULL argument";
+  if (B < 1 || B > max_batch) return "B outside [1, max_batch]";
+  for (int32_t p = 0; p < B; ++p)
+    if (model_idx[p] < 0 || model_idx[p] >= n) return "a model index outside [0, n)";
+  return nullptr;
+}
+
 // The polled completion's wait bound in s_memrealtime ticks (100 MHz): a 2 s floor plus
 // 40 ns per look-ahead rollout step of the launch (a rate floor of 2.5e7 steps/s, ~10^3
 // below the fast path's, so the general-path re-runs, the raceline walker and launches
@@ -284,6 +382,28 @@ inline int spin_for_tag(const uint64_t* tag, uint64_t want, OnTimeout on_timeout
     if ((++spins & 0xFFF) == 0 && std::chrono::steady_clock::now() - t0 > bound) {
       if (int rc = on_timeout()) return rc;
       return __atomic_load_n(tag, __ATOMIC_ACQUIRE) == want ? 0 : kSpinTimeout;
+    }
+  }
+  return 0;
+}
+
+// spin_for_tag for the B tags tag[p stride] of one launch under ONE bound: arrived[p] says whether
+// tag p carries `want` (acquire).  After `bound`, on_timeout() runs once (its non-zero return is
+// passed on) and the tags still missing are read one last time without waiting.
+template <class OnTimeout>
+inline int spin_for_tags(const uint64_t* tag, size_t stride, int32_t B, uint64_t want, bool* arrived,
+                         OnTimeout on_timeout, std::chrono::nanoseconds bound = std::chrono::seconds(10)) {
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t spins = 0;
+  bool expired = false;
+  for (int32_t p = 0; p < B; ++p) {
+    const uint64_t* t = tag + (size_t)p * stride;
+    while (!(arrived[p] = __atomic_load_n(t, __ATOMIC_ACQUIRE) == want) && !expired) {
+      __builtin_ia32_pause();
+      if ((++spins & 0xFFF) == 0 && std::chrono::steady_clock::now() - t0 > bound) {
+        if (int rc = on_timeout()) return rc;
+        expired = true;
+      }
     }
   }
   return 0;

@@ -40,6 +40,18 @@ struct __attribute__((visibility("hidden"))) llampc_nlp {
   std::mutex mu;
 };
 
+// The cfg checks of llampc_nlp_create and llampc_nlp_batch_create.
+int nlp_check_cfg(const llampc_nlp_cfg& k) {
+  if (k.H < 1 || k.H > LLAMPC_HMAX) return fail(LLAMPC_E_ARG, "H=%d outside [1, %d]", k.H, LLAMPC_HMAX);
+  if (k.samples < 64 || k.samples > 4096 || (k.samples & (k.samples - 1)))
+    return fail(LLAMPC_E_ARG, "samples=%d: a power of two in [64, 4096]", k.samples);
+  if (k.elite < 1 || k.elite > 64 || k.elite > k.samples || k.iters < 1 || k.iters > kNlpMaxIters)
+    return fail(LLAMPC_E_ARG, "elite=%d (1..64, <= samples) iters=%d (1..%d)", k.elite, k.iters, kNlpMaxIters);
+  if (!(k.Ts > 0) || !std::isfinite(k.Ts)) return fail(LLAMPC_E_ARG, "Ts must be finite > 0");
+  if (nlp_lds_bytes(k.H, k.samples, k.elite) > 160 * 1024) return fail(LLAMPC_E_ARG, "H x elite too large for LDS");
+  return LLAMPC_OK;
+}
+
 extern "C" {
 
 int llampc_nlp_destroy(llampc_nlp* p) {
@@ -56,13 +68,7 @@ int llampc_nlp_create(llampc_bank* b, const llampc_nlp_cfg* cfg, llampc_nlp** ou
   if (!b || !cfg) return fail(LLAMPC_E_ARG, "NULL argument");
   const llampc_nlp_cfg& k = *cfg;
   if (b->n != 1) return fail(LLAMPC_E_ARG, "the NLP solver's bank holds one model (n=%lld)", (long long)b->n);
-  if (k.H < 1 || k.H > LLAMPC_HMAX) return fail(LLAMPC_E_ARG, "H=%d outside [1, %d]", k.H, LLAMPC_HMAX);
-  if (k.samples < 64 || k.samples > 4096 || (k.samples & (k.samples - 1)))
-    return fail(LLAMPC_E_ARG, "samples=%d: a power of two in [64, 4096]", k.samples);
-  if (k.elite < 1 || k.elite > 64 || k.elite > k.samples || k.iters < 1 || k.iters > kNlpMaxIters)
-    return fail(LLAMPC_E_ARG, "elite=%d (1..64, <= samples) iters=%d (1..%d)", k.elite, k.iters, kNlpMaxIters);
-  if (!(k.Ts > 0) || !std::isfinite(k.Ts)) return fail(LLAMPC_E_ARG, "Ts must be finite > 0");
-  if (nlp_lds_bytes(k.H, k.samples, k.elite) > 160 * 1024) return fail(LLAMPC_E_ARG, "H x elite too large for LDS");
+  if (int rc = nlp_check_cfg(k)) return rc;
   DeviceGuard g(b->device);
   Building<llampc_nlp> p(new llampc_nlp(), llampc_nlp_destroy);
   p->b = b;
@@ -198,14 +204,7 @@ static int nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
   for (int i = 0; i < H; ++i)
     for (int j = 0; j < 2; ++j) m0[2 * i + j] = base ? base[2 * i + j] : uprev[j];
   NlpLaunch a{};
-  a.la.params = b->d_params.get();
-  a.la.n = 1;
-  a.la.veh = integrator_veh(b->veh, LLAMPC_EULER_NLP);
-  a.la.C = 64;
-  a.la.H = H;
-  a.la.integrator = LLAMPC_EULER_NLP;
-  a.la.Ts = k.Ts;
-  a.la.cost = make_cost(k.cost, k.Ts);
+  nlp_launch_cfg(a, k, b->veh, b->d_params.get(), 1);
   a.st = p->d_st.get();
   a.list_tag = reinterpret_cast<uint64_t*>(p->d_cost.get());
   a.cand = p->d_cost.get() + 6 * (size_t)k.samples;
@@ -218,22 +217,7 @@ static int nlp_solve(llampc_nlp* p, const double* x0, const double* xref, const 
   a.call = p->calls;
   a.up0 = uprev[0];
   a.up1 = uprev[1];
-  a.umin0 = k.cost.umin[0];
-  a.umin1 = k.cost.umin[1];
-  a.umax0 = k.cost.umax[0];
-  a.umax1 = k.cost.umax[1];
-  a.rlo0 = k.rate_lo[0];
-  a.rlo1 = k.rate_lo[1];
-  a.rhi0 = k.rate_hi[0];
-  a.rhi1 = k.rate_hi[1];
-  a.std_floor = k.std_floor;
-  a.sig0 = k.sigma0[0];
-  a.sig1 = k.sigma0[1];
-  a.H = H;
-  a.samples = k.samples;
-  a.elite = k.elite;
   a.has_hold = has_hold;
-  a.iters = k.iters;                    // the last round's completion writes xmpc (nmpc.py:58-60)
   if (p->per_round) {
     a.rounds = 1;
     for (int it = 0; it < k.iters; ++it) {

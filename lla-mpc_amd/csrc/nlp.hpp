@@ -1,4 +1,5 @@
-// nlp.hpp — the setupNLP.solve drop-in's launch interface (nlp.hip; llampc_nlp_* in capi.hip).
+// nlp.hpp — the setupNLP.solve drop-in's launch interface (nlp.hip, nlp_batch.hip; llampc_nlp_* in
+// capi_nlp.hip, llampc_nlp_batch_* in capi_nlp_batch.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -103,5 +104,25 @@ struct NlpCorridor {
 size_t nlp_corridor_lds_bytes(int H, int samples, int elite, bool ltraj = false);
 bool nlp_corridor_ltraj_fits(int H, int samples, int elite);   // else the re-run trajectory
 hipError_t launch_nlp_corridor(const NlpLaunch& a, const NlpInline& pk, const NlpCorridor& cor, hipStream_t s);
+
+// The batched solve's own argument (llampc_nlp_batch_solve; nlp_batch.hip): B independent
+// problems in one launch of B x nl blocks (nl = samples / 64, a power of two), block g being
+// block g % nl of problem p = g / nl.  NlpLaunch carries problem 0's pointers and what the batch
+// shares (the bank's params [6][n] and vehicle, the cost, the bounds, the shape, host_seq, call);
+// problem p's words lie p strides on: st[p], res[p], host_tag[p tag_words], list_tag + p
+// list_words, ms_tag + p ms_words, cand + p cand_doubles.  Its inputs are record p of `in` (the
+// device alias of a pinned mapped buffer the host writes before the launch; B of them do not fit
+// the kernarg segment), 64-bit words: x0 [6] | xref [2][H+1] | the first mean [H][2] (NlpInline's
+// layout) | at up_off: uprev [2] | the Philox seed | model index (low half), has_hold (high).
+// The strides and offsets are capi_host.hpp nlp_batch_layout's.
+struct NlpBatch {
+  const uint64_t* in;
+  uint64_t cand_doubles;
+  uint32_t rec_words, up_off, list_words, ms_words, tag_words;
+  int32_t nl_log2;
+};
+static_assert(sizeof(NlpBatch) == 40 && alignof(NlpBatch) == 8, "NlpBatch layout (a kernel argument)");
+// B x nl blocks, all co-resident (the caller has checked B nl against the CU count)
+hipError_t launch_nlp_batch(const NlpLaunch& a, const NlpBatch& bt, int B, hipStream_t s);
 
 }  // namespace llampc

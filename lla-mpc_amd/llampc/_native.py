@@ -21,6 +21,7 @@ NAN_FIRST, NAN_IGNORE = 0, 1
 XREF_GIVEN, XREF_RACELINE = 0, 1
 OP_FORCES, OP_DERIV = 0, 1
 E_ARG, E_HIP, E_NODEV, E_STATE, E_OOM, E_DEVICE = -1, -2, -3, -4, -5, -6
+NLP_OK, NLP_NO_FINITE, NLP_NO_TAG = 0, 1, 2      # llampc_nlp_status
 
 
 class NativeError(RuntimeError):
@@ -181,6 +182,12 @@ _SIGNATURES = {
                                          C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     "llampc_nlp_destroy": (C.c_int, [C.c_void_p]),
+    "llampc_nlp_batch_create": (C.c_int, [C.c_void_p, C.POINTER(NlpCfg), C.c_int32, C.POINTER(C.c_void_p)]),
+    "llampc_nlp_batch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # B, model_idx [B] (int64), seed [B] (uint64) or NULL, x0, xref, uprev, base or NULL, has_hold [B]
+    # (int32) -> umpc, fval, xmpc, status [B] (int32)
+    "llampc_nlp_batch_solve": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 11),
+    "llampc_nlp_batch_destroy": (C.c_int, [C.c_void_p]),
     "llampc_dynamics_batch": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.POINTER(Vehicle), C.c_int64, C.c_void_p, C.c_int32,
                                         C.c_int32, C.c_void_p]),

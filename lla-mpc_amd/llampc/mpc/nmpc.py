@@ -67,6 +67,38 @@ def _attr(model, k, default=None):
     return getattr(model, k, default)
 
 
+def _bounds_cost(params, Ts, Q, R, P):
+    """(umin, umax, rate, cost) as the solvers read them from ``params``: the input bounds, the
+    per-step rate bounds [(lo Ts, hi Ts) or (None, None)] and the llampc_cost."""
+    umin = np.asarray(params["min_inputs"], dtype=np.float64)
+    umax = np.asarray(params["max_inputs"], dtype=np.float64)
+    # rate bounds min_rates[j]*Ts <= d u_j <= max_rates[j]*Ts (nmpc.py:104-105: the steering
+    # rate; ORCA leaves the pwm rate None, unconstrained).  The kernel's feasibility test is
+    # symmetric, |du| <= rate_max*Ts: an asymmetric pair is narrowed to its tighter side
+    # m = min(-lo, hi), and the rate chain clips to the same [-m, +m]*Ts — every sample it
+    # produces is then feasible by construction (module doc).
+    rate_max = tuple(-1.0 if lo is None else min(-float(lo), float(hi))
+                     for lo, hi in zip(params["min_rates"], params["max_rates"]))
+    if any(lo is not None and not m >= 0 for m, lo in zip(rate_max, params["min_rates"])):
+        raise ValueError("min_rates must be <= 0 <= max_rates (the symmetric rate bound min(-lo, hi))")
+    rate = [(None, None) if m < 0 else (-m * Ts, m * Ts) for m in rate_max]
+    cost = nat.cost_struct(Q=Q, R=R, P=P, umin=umin, umax=umax, rate_max=rate_max, enforce_bounds=True)
+    return umin, umax, rate, cost
+
+
+def _nlp_cfg(s):
+    """llampc_nlp_cfg of a solver object (its horizon, samples, iters, elite, Ts, std_floor, seed,
+    sigma, cost and rate)."""
+    cfg = nat.NlpCfg()
+    cfg.H, cfg.samples, cfg.iters, cfg.elite = s.horizon, s.samples, s.iters, s.elite
+    cfg.Ts, cfg.std_floor, cfg.seed = s.Ts, s.std_floor, s.seed
+    cfg.sigma0[0], cfg.sigma0[1] = float(s.sigma[0]), float(s.sigma[1])
+    cfg.cost = s.cost
+    for j, (lo, hi) in enumerate(s.rate):
+        cfg.rate_lo[j], cfg.rate_hi[j] = (1.0, -1.0) if lo is None else (lo, hi)
+    return cfg
+
+
 class setupNLP:
     """Same constructor and ``solve`` contract as nmpc.py:14-203 (see module doc)."""
 
@@ -99,20 +131,7 @@ class setupNLP:
         self.samples, self.iters, self.elite = int(samples), int(iters), int(elite)
         self.sigma = np.asarray(sigma, dtype=np.float64)
         self.std_floor, self.seed, self.device = float(std_floor), int(seed), device
-        self.umin = np.asarray(params["min_inputs"], dtype=np.float64)
-        self.umax = np.asarray(params["max_inputs"], dtype=np.float64)
-        # rate bounds min_rates[j]*Ts <= d u_j <= max_rates[j]*Ts (nmpc.py:104-105: the steering
-        # rate; ORCA leaves the pwm rate None, unconstrained).  The kernel's feasibility test is
-        # symmetric, |du| <= rate_max*Ts: an asymmetric pair is narrowed to its tighter side
-        # m = min(-lo, hi), and the rate chain clips to the same [-m, +m]*Ts — every sample it
-        # produces is then feasible by construction (module doc).
-        rate_max = tuple(-1.0 if lo is None else min(-float(lo), float(hi))
-                         for lo, hi in zip(params["min_rates"], params["max_rates"]))
-        if any(lo is not None and not m >= 0 for m, lo in zip(rate_max, params["min_rates"])):
-            raise ValueError("min_rates must be <= 0 <= max_rates (the symmetric rate bound min(-lo, hi))")
-        self.rate = [(None, None) if m < 0 else (-m * self.Ts, m * self.Ts) for m in rate_max]
-        self.cost = nat.cost_struct(Q=Q, R=R, P=P, umin=self.umin, umax=self.umax,
-                                    rate_max=rate_max, enforce_bounds=True)
+        self.umin, self.umax, self.rate, self.cost = _bounds_cost(params, self.Ts, Q, R, P)
         self._bank = None
         self._h = None
         self._dyn = None
@@ -131,13 +150,7 @@ class setupNLP:
             p6 = np.nan_to_num(p6)
         self._bank = ModelBank(p6, shared=shared, W=1, device=self.device,
                                input_acc=bool(_attr(m, "input_acc", False)), approx=approx)
-        cfg = nat.NlpCfg()
-        cfg.H, cfg.samples, cfg.iters, cfg.elite = self.horizon, self.samples, self.iters, self.elite
-        cfg.Ts, cfg.std_floor, cfg.seed = self.Ts, self.std_floor, self.seed
-        cfg.sigma0[0], cfg.sigma0[1] = float(self.sigma[0]), float(self.sigma[1])
-        cfg.cost = self.cost
-        for j, (lo, hi) in enumerate(self.rate):
-            cfg.rate_lo[j], cfg.rate_hi[j] = (1.0, -1.0) if lo is None else (lo, hi)
+        cfg = _nlp_cfg(self)
         h = nat.C.c_void_p()
         nat.check(nat.load().llampc_nlp_create(self._bank.handle, nat.C.byref(cfg), nat.C.byref(h)))
         self._h = h
@@ -245,6 +258,133 @@ class setupNLP:
         if self._bank is not None:
             self._bank.close()
             self._bank = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class setupNLPBatch:
+    """One solver bound to a whole ``ModelBank``: ``solve`` runs B independent NMPC problems, each
+    with its own bank model (by index), state, reference, previous input, warm start and noise
+    seed, in ONE launch (llampc_nlp_batch_solve, csrc/nlp_batch.hip), each on its own samples / 64
+    blocks.  The reference builds one setupNLP per bank model (rt.py:195-202) and solves with the
+    one the look-back selected (rt.py:305); here the index from ``plan()`` / ``LLAMPC.tick`` (and
+    the top-K's, or a second track's car) goes straight into ``models``.
+
+    A problem's search is ``setupNLP.solve``'s bit for bit: problem p of the solver's c-th launch
+    equals the c-th solve of a ``setupNLP`` built on bank column ``models[p]`` with ``seeds[p]``.
+
+    ``bank`` is borrowed (``close()`` leaves it open; close the solver first).  Bounds and rates are
+    read from ``params`` as setupNLP reads them.  **Slot p is a car, not a model**: slot p's warm
+    start is slot p's previous ``umpc`` shifted one step, whatever model it uses this time; a slot
+    whose last solve failed, or that ``reset`` dropped, starts cold.
+
+    The problems' blocks wait for each other's rounds, so a launch of B problems needs (and holds
+    for the solve's duration) B x samples / 64 CUs: ``max_batch`` x samples / 64 must not exceed the
+    device's CU count (refused at construction), and a ``solve`` of more than ``max_batch`` problems
+    or of more than ``max_resident`` blocks (default: the CU count; lower it for co-tenants) is
+    issued as consecutive launches of as many problems as fit.  Chunking changes no result bit of a
+    first solve; each chunk consumes one solve number (the Philox call word), and the chunk counts
+    follow from the shapes alone, so call numbers stay deterministic: problem p of a chunked solve
+    is in chunk p // per_launch, whose number is the count of launches before it."""
+
+    def __init__(self, horizon, Ts, Q, P, R, params, bank, max_batch=8, samples=1024, iters=8, elite=32,
+                 sigma=(0.3, 0.15), std_floor=1e-4, seed=0, max_resident=None):
+        if not isinstance(bank, ModelBank):
+            raise TypeError("bank must be a ModelBank")
+        self.horizon, self.Ts = int(horizon), float(Ts)
+        self.params, self.bank, self.max_batch = params, bank, int(max_batch)
+        self.samples, self.iters, self.elite = int(samples), int(iters), int(elite)
+        self.sigma = np.asarray(sigma, dtype=np.float64)
+        self.std_floor, self.seed = float(std_floor), int(seed)
+        self.umin, self.umax, self.rate, self.cost = _bounds_cost(params, self.Ts, Q, R, P)
+        self._h = None
+        self.cfg = _nlp_cfg(self)
+        h = nat.C.c_void_p()
+        nat.check(nat.load().llampc_nlp_batch_create(bank.handle, nat.C.byref(self.cfg), self.max_batch,
+                                                     nat.C.byref(h)))
+        self._h = h
+        cus = nat.C.c_int32()
+        nat.check(nat.load().llampc_nlp_batch_info(h, None, nat.C.byref(cus)))
+        self.cus = cus.value
+        self.max_resident = self.cus if max_resident is None else int(max_resident)
+        nl = self.samples // 64
+        if self.max_resident < nl:
+            self.close()
+            raise ValueError(f"max_resident={self.max_resident} holds no problem ({nl} blocks each)")
+        self.per_launch = min(self.max_batch, self.max_resident // nl)     # problems per launch
+        self._last = {}              # slot -> previous umpc [H, 2] (absent: cold)
+
+    def reset(self, slots=None):
+        """Drops the warm starts of ``slots`` (None: all)."""
+        if slots is None:
+            self._last.clear()
+        else:
+            for p in slots:
+                self._last.pop(int(p), None)
+
+    def solve(self, models, x0, xref, uprev, seeds=None):
+        """models [B] bank indices, x0 [B, 6], xref [B, 2, H+1] (or [2, H+1] shared), uprev [B, 2],
+        seeds [B] (None: the solver's seed for all) -> (umpc [B, 2, H], fval [B], xmpc [B, 6, H+1],
+        ok [B]).  A problem that found no finite objective, or whose completion never arrived, has
+        ok False, umpc zeros and fval inf, and does not disturb the others."""
+        if self._h is None:
+            raise nat.NativeError("solver is closed")
+        H = self.horizon
+        models = np.ascontiguousarray(models, dtype=np.int64)
+        if models.ndim != 1 or models.size < 1:
+            raise ValueError(f"models must be a non-empty 1-d sequence of bank indices, got shape {models.shape}")
+        B = models.size
+        if np.any(models < 0) or np.any(models >= self.bank.n):
+            raise ValueError(f"models must lie in [0, {self.bank.n}), got {models.tolist()}")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0.shape != (B, 6):
+            raise ValueError(f"x0 must be [B, 6] = {(B, 6)}, got {x0.shape}")
+        xref = np.asarray(xref, dtype=np.float64)
+        if xref.shape == (2, H + 1):
+            xref = np.broadcast_to(xref, (B, 2, H + 1))
+        if xref.shape != (B, 2, H + 1):
+            raise ValueError(f"xref must be [B, 2, H+1] = {(B, 2, H + 1)} or [2, H+1], got {xref.shape}")
+        xref = np.ascontiguousarray(xref)
+        uprev = np.ascontiguousarray(uprev, dtype=np.float64)
+        if uprev.shape != (B, 2):
+            raise ValueError(f"uprev must be [B, 2] = {(B, 2)}, got {uprev.shape}")
+        if seeds is None:
+            seeds = np.full(B, self.seed, dtype=np.uint64)
+        else:
+            seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if seeds.shape != (B,):
+                raise ValueError(f"seeds must be [B] = {(B,)}, got {seeds.shape}")
+        hold = np.array([p in self._last for p in range(B)], dtype=np.int32)
+        base = np.zeros((B, H, 2))
+        for p in range(B):
+            if hold[p]:                  # the warm start: the slot's last solution shifted one step
+                base[p, :-1] = self._last[p][1:]
+                base[p, -1] = self._last[p][-1]
+        umpc, fval = np.zeros((B, H, 2)), np.zeros(B)
+        xmpc, status = np.zeros((B, H + 1, 6)), np.zeros(B, dtype=np.int32)
+        lib = nat.load()
+        for lo in range(0, B, self.per_launch):
+            hi = min(B, lo + self.per_launch)
+            nat.check(lib.llampc_nlp_batch_solve(
+                self._h, hi - lo, models[lo:hi].ctypes.data, seeds[lo:hi].ctypes.data, x0[lo:hi].ctypes.data,
+                xref[lo:hi].ctypes.data, uprev[lo:hi].ctypes.data, base[lo:hi].ctypes.data, hold[lo:hi].ctypes.data,
+                umpc[lo:hi].ctypes.data, fval[lo:hi].ctypes.data, xmpc[lo:hi].ctypes.data, status[lo:hi].ctypes.data))
+        ok = status == nat.NLP_OK
+        for p in range(B):
+            if ok[p]:
+                self._last[p] = umpc[p].copy()
+            else:
+                self._last.pop(p, None)
+        return np.ascontiguousarray(umpc.transpose(0, 2, 1)), fval, np.ascontiguousarray(xmpc.transpose(0, 2, 1)), ok
+
+    def close(self):
+        if self._h is not None:
+            nat.load().llampc_nlp_batch_destroy(self._h)
+            self._h = None
 
     def __del__(self):
         try:
