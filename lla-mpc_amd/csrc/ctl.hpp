@@ -355,7 +355,7 @@ struct CtlLaunch {
   // armed ticks with the peer exchange and n_spec > 0: every rank's speculative list goes
   // through the mailbox slot too, at word px_spec_off (after the selection record), before the
   // doorbell; a peer's list that is not there after px_spec_wait s_memrealtime ticks is not
-  // waited for (ctl.hip ctl_spec_exchange)
+  // waited for (ctl_spec_dev.hpp ctl_spec_exchange)
   int32_t px_spec_off;
   uint32_t px_spec_wait;
   // armed launch (door != null, llampc_ctl_set_prelaunch): enqueued behind the previous tick,

@@ -1,7 +1,7 @@
 // dev_stamps.hpp — the diagnostic stamps of the device code: the LLAMPC_STAMPS globals and the
-// STAMP / LA_STAMP / LB_STAMP / RL_STAMP / STEP_STAMP / WQ_STAMP macros, which expand to
-// nothing in the product build.  Included by every device header that stamps a phase; the
-// llampc_debug_* readers of the globals are in plan_rk4_l4.hip and plan_rk4_l1.hip.
+// STAMP / LA_STAMP / LB_STAMP / RL_STAMP / STEP_STAMP / WQ_STAMP / CTL_STAMP macros, which
+// expand to nothing in the product build.  Included by every device header that stamps a phase;
+// the llampc_debug_* readers of the globals are in plan_rk4_l4.hip, plan_rk4_l1.hip and ctl.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,6 +71,19 @@ static __device__ unsigned long long g_wq_unit[256][8][16][4][2];
       g_wq_unit[blk][threadIdx.x >> 6][j][slot][1] = __builtin_amdgcn_s_memrealtime();   \
     }                                                                                    \
   } while (0)
+// The controller tick (ctl.hip): s_memrealtime (100 MHz) per block and phase of the last launch
+// (tools/diag/ctl_phases.py; the reader, llampc_debug_ctl_stamps, is in ctl.hip).  Look-ahead
+// blocks: 0 entry, 1 staged, 10 walk done, 2 walk
+// barrier, 3 selection, 4 rolled out, 5 published; look-back blocks: 0 entry, 6 scored,
+// 7 lb_final done (ticket winner), 8 slots polled, 12 top-K / sequence stores issued, 13 the
+// record words computed, 11 record stores issued, 9 record written; look-ahead prologue: 14 the
+// mu bracket known, 15 the tables' LDS stores issued; 16 an armed launch's doorbell seen; the
+// walk (cs_walk_wave): 17 its loop entered, 18 its loop done (then x/y).
+static __device__ unsigned long long g_ctl_ph[64][24];
+#define CTL_STAMP(blk, slot)                                                                   \
+  do {                                                                                         \
+    if (threadIdx.x == 0 && (blk) < 64) g_ctl_ph[blk][slot] = __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
 #else
 #define LLAMPC_NO_STAMP \
   do {                  \
@@ -81,6 +94,7 @@ static __device__ unsigned long long g_wq_unit[256][8][16][4][2];
 #define LA_STAMP(blk, slot) LLAMPC_NO_STAMP
 #define RL_STAMP(blk, slot) LLAMPC_NO_STAMP
 #define LB_STAMP(blk, slot) LLAMPC_NO_STAMP
+#define CTL_STAMP(blk, slot) LLAMPC_NO_STAMP
 #endif
 
 }  // namespace llampc

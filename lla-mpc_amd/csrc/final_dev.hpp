@@ -66,7 +66,7 @@ __device__ __forceinline__ E* tree_merge(E* buf0, E* buf1, int L, int K) {
 // The controller tick's use of lb_final (SEL = true, ctl.hip): the selection is also published
 // for the look-ahead blocks waiting on it — tagged words [K + 1] (local model index of top-K
 // entry k, kNoLocal = none; entry K: the argmin) — and kept in LDS for the completion.
-// SEL = 2 (the sharded controller, ctl.hip ctl_exchange): nothing is published and no record
+// SEL = 2 (the sharded controller, ctl_complete_dev.hpp ctl_exchange): nothing is published and no record
 // field written — the shard's top-K and argmin (local index, value) go to ids / xv for the
 // exchange, which publishes the MERGED selection.
 struct CtlSel {

@@ -521,6 +521,8 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
         J = rollout<INTEG, LPM, kRF | kRFast | kRSplitQ>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, bad);
       else
         J = rollout<INTEG, LPM, kRF | kRFast>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, bad);
+      // merge_bad<LPM>(bad) (rollout_dev.hpp), open-coded: the call changes this kernel's
+      // register allocation
       if (LPM == 2) {                   // the pair shares one rollout: re-run both or neither
         const int bi = bad;
         bad = __builtin_amdgcn_mov_dpp(bi, kPair0, 0xF, 0xF, false) |

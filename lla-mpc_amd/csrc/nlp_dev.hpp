@@ -258,10 +258,8 @@ __device__ __forceinline__ void nlp_traj_quad(const NlpLaunch& a, const double* 
   constexpr unsigned kRF = kRUlds | kRTraj;                 // the re-run; the fast run adds kRFast
   bool bad = false;
   (void)rollout<1, LPM, kRF | kRFast>(a.la, 0, 0, x0, sx, ub, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad, out);
-  int bi = bad;
-  bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX1, 0xF, 0xF, false);
-  bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX2, 0xF, 0xF, false);
-  if (bi) {
+  merge_bad<LPM>(bad);
+  if (bad) {
     bool unused = false;
     (void)rollout<1, LPM, kRF>(a.la, 0, 0, x0, sx, ub, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused, out);
   }
@@ -903,6 +901,7 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk, Ext.
     CostK q = a.la.cost;
     VehK veh = a.la.veh;
     double Ts = a.la.Ts;
+    // the pins of the look-ahead blocks without the vehicle (veh stays unpinned here)
     for (int m = 0; m < 4; ++m) {
       pin_vgpr(q.Q[m]);
       pin_vgpr(q.R[m]);
@@ -931,12 +930,10 @@ __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk, Ext.
     else
       J = rollout<1, LPM, kRF | kRFast>(a.la, c, 0, x0, sx, Ul, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, bad, nullptr,
                                         nullptr, nullptr, 0, nullptr, shp, cw);
-    int bi = bad;
-    bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX1, 0xF, 0xF, false);
-    bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX2, 0xF, 0xF, false);
-    if (__builtin_expect(__any(bi), 0)) {
+    merge_bad<LPM>(bad);
+    if (__builtin_expect(__any(bad), 0)) {
       bool unused = false;
-      if (bi) {
+      if (bad) {
         if constexpr (ST)
           J = rollout<1, LPM, kRF, kNlpStageW>(a.la, c, 0, x0, sx, su, veh, t, sk, q, Ts, a.up0, a.up1, K, fq, unused, tj,
                                            nullptr, nullptr, 0, nullptr, shp, cw);

@@ -1,6 +1,6 @@
 // rollout_dev.hpp — one (model, candidate) rollout over the horizon with its NLP objective, in
 // every compile-time variant (the RolloutFlag bits), and what its callers share: load_tire, the
-// input-rate term, the input feasibility and the batched global -> LDS copy.  Included by
+// input-rate term, the input feasibility, the pair / quad merge of `bad` and the batched global -> LDS copy.  Included by
 // lookback_dev.hpp, lookahead_dev.hpp, ctl.hip, nlp.hip and kernels.hip.
 #pragma once
 #include "dev_stamps.hpp"
@@ -36,6 +36,21 @@ __device__ __forceinline__ bool input_feasible(const CostK& q, double ua, double
          ((int)(q.dmax[1] < 0) | (int)(fabs(d1) <= q.dmax[1]));
 }
 
+// The pair or quad of one rollout shares it: the lanes' `bad` flags merged by DPP, so that the
+// general evaluation re-runs in all of the rollout's lanes or in none (in place; LPM 1: nothing).
+template <int LPM>
+__device__ __forceinline__ void merge_bad(bool& bad) {
+  if (LPM == 2) {
+    const int bi = bad;
+    bad = __builtin_amdgcn_mov_dpp(bi, kPair0, 0xF, 0xF, false) | __builtin_amdgcn_mov_dpp(bi, kPair1, 0xF, 0xF, false);
+  } else if (LPM == 4) {
+    int bi = bad;
+    bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX1, 0xF, 0xF, false);
+    bi |= __builtin_amdgcn_mov_dpp(bi, kQuadX2, 0xF, 0xF, false);
+    bad = bi;
+  }
+}
+
 // The corridor term of one step (CORR): hp = (a0, a1, b, c0, c1, d), the half-planes a.p <= b and
 // c.p <= d on the position p = (X, Y) after the step; the squared slacks s1^2 + s2^2, every
 // product and sum rounded on its own.  a = 0, b = +inf disables a half-plane (g = -inf, s = 0;
@@ -64,10 +79,10 @@ enum RolloutFlag : unsigned {
                       //   without it the general evaluation: the re-run of bad lanes, on the lane's own operands only
   kRSplit = 1u << 3,  // SPLIT (fused RK4, LPM 4, diagonal Q and P): a quad lane integrates one position component
                       //   (dyn.hpp k_fused) and its tracking term; J = (J_X + J_Y) + act by two DPP broadcasts
-  kRUlds = 1u << 4,   // ULDS (ctl.hip, nlp.hip): the raw candidates U [C][H][2] at `su` (LDS) instead of a.U
+  kRUlds = 1u << 4,   // ULDS (the controller tick, nlp.hip): the raw candidates U [C][H][2] at `su` (LDS) instead of a.U
   kRTraj = 1u << 5,   // TRAJ: the state after every step to `traj` (three 16-B stores; null: none)
-  kRS4 = 1u << 6,     // S4 (ctl.hip ctl_stage, with ULDS and FAST): sin / cos delta and the cost terms read at `s4`
-  kRDefer = 1u << 7,  // DEFER (ctl.hip ctl_spec, with SPLIT and S4): positions to `dpos`, the rest to *dout
+  kRS4 = 1u << 6,     // S4 (ctl_cand_dev.hpp ctl_stage, with ULDS and FAST): sin / cos delta and the cost terms read at `s4`
+  kRDefer = 1u << 7,  // DEFER (ctl_spec_dev.hpp ctl_spec, with SPLIT and S4): positions to `dpos`, the rest to *dout
   kRCorr = 1u << 8,   // CORR (nlp.hip's corridor solve): two position half-planes per step at `hp` [H][6] (LDS), the
                       //   squared slacks summed over the horizon, J + cw pen (corridor_slack2 below)
   kRQuadr = 1u << 9,  // QUADR (with SPLIT; the plan kernel's lookahead_block): the component is a per-step quadrature in
@@ -77,7 +92,7 @@ enum RolloutFlag : unsigned {
 // What DEFER returns in *dout: the reference is not known yet, so the lane stores its position
 // component after step k at dpos[k dstride] instead of accumulating the tracking term, and
 // returns its last position, the summed input-rate cost, the feasibility and the domain flag
-// (J: ctl.hip defer_cost, the same terms in the same order once the reference is known).
+// (J: ctl_spec_dev.hpp defer_cost, the same terms in the same order once the reference is known).
 struct DeferOut {
   double xl, act, feas_s;
   bool dok;

@@ -100,7 +100,7 @@ class MuEstimator:
 
     def record(self, dr_mean, df_mean, mu_pred, warm):
         """The device controller's update of this tick (it computed the same values on the
-        GPU, ctl.hip ctl_complete): the histories, mu-hat and the logged smoothed value."""
+        GPU, ctl_complete_dev.hpp ctl_complete): the histories, mu-hat and the logged smoothed value."""
         self.dr_hist.append(dr_mean)
         self.df_hist.append(df_mean)
         if warm:

@@ -225,7 +225,7 @@ def test_ctl_two_tracks_async_equal_sequential(nat):
 
 def test_ctl_staged_inputs_equal_unstaged(nat, monkeypatch):
     """The look-ahead's staged input terms (sin / cos delta per (candidate, step), the summed
-    input-rate cost and feasibility per candidate, ctl.hip ctl_stage) against the rollout
+    input-rate cost and feasibility per candidate, ctl_cand_dev.hpp ctl_stage) against the rollout
     forming them per step (LLAMPC_CTL_NO_STAGE=1 at create): the same records, bitwise, over
     ticks through the warm-up and the selection, with the variates of ticks >= 1 drawn one tick
     ahead by the completion (ctl_draw_next) and those of tick 0 in the launch."""
