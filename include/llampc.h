@@ -19,6 +19,9 @@
  *                                  (llampc/mpc/nmpc.py:44-111) + argmin
  *  llampc_plan / llampc_plan_device one LLA-MPC tick: rt.py:300-366 (look-back on the
  *                                  newest transition, selection, look-ahead from x_t)
+ *  llampc_plan_corridor,           (new) llampc_plan / llampc_lookahead with soft per-step track
+ *  llampc_lookahead_corridor       half-planes on every rollout's positions (the half-planes of
+ *                                  llampc_nlp_solve_corridor; rt.py:63 runs TRACK_CONS = False)
  *  llampc_merge / _device          (new) cross-shard merge of per-GPU plan results
  *  llampc_exchange_rccl / _peer    (new) the per-tick gather + merge of the sharded bank
  *                                  (SURVEY.md §8e): RCCL all-gather, or xGMI mailboxes
@@ -231,6 +234,34 @@ int llampc_lookahead(llampc_bank* bank, const double* x0, const double* U, int32
 int llampc_plan_variant(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share,
                         int32_t out[4]);
 
+/* llampc_lookahead under a soft track corridor (extends llampc_lookahead; the half-planes are
+ * llampc_nlp_solve_corridor's): hp [H][6], row k - 1 = (a0, a1, b, c0, c1, d), the half-planes
+ * a.p_k <= b and c.p_k <= d on the position p_k = (X, Y) after k steps of the launch's own
+ * integrator, k = 1..H (a = (0, 0), b = +inf disables one).  Every (model, candidate) cost becomes
+ *   J_c = J + weight x sum_k max(a.p_k - b, 0)^2 + max(c.p_k - d, 0)^2
+ * (k ascending, every product and sum rounded on its own, weight x pen added last, after the
+ * terminal and input-rate terms); a candidate infeasible under cost.enforce_bounds still costs
+ * +inf, and the per-model argmin, the global best, the non-finite count and the tie-breaking are
+ * llampc_lookahead's, applied to J_c.  Replaces nothing in the reference (its look-ahead is the
+ * NLP solve, whose track constraints constraints.py holds; rt.py:63 runs without them).
+ * Integrators: LLAMPC_RK4 and LLAMPC_EULER_NLP.  The launch rolls every pair out with both position
+ * components in one lane (at 4 lanes per rollout too, where llampc_lookahead splits them for
+ * diagonal Q and P), one block per group of models — never the work-queue layout.
+ * LLAMPC_E_ARG, with nothing enqueued and the bank's launch counter unchanged: hp NULL, LLAMPC_RK6,
+ * a non-finite normal component, an offset NaN or -inf, a weight negative or non-finite. */
+int llampc_lookahead_corridor(llampc_bank* bank, const double* x0, const double* U, int32_t C,
+                              int32_t H, const double* xref, const double* uprev,
+                              const llampc_cost* cost, double Ts, int32_t integrator,
+                              double* cost_out, int32_t* best_cand_out, int64_t* best_model,
+                              int32_t* best_cand, double* best_cost,
+                              const double* hp /* [H][6] */, double weight);
+/* llampc_plan_variant for a corridor launch (llampc_lookahead_corridor, llampc_plan_corridor) —
+ * host only, from the functions the launch calls: out = {lpm, G, cpl, stage}; stage counts the
+ * corridor's 48 H bytes of LDS, so a shape llampc_plan_variant reports staged may be unstaged
+ * here.  LLAMPC_E_ARG also for LLAMPC_RK6. */
+int llampc_plan_variant_corridor(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share,
+                                 int32_t out[4]);
+
 /* Attach (replace) the raceline library used by LLAMPC_XREF_RACELINE: natural cubic
  * splines over the arc length (pycubicspline.py:17-182, track.py:52-83): knots [n]
  * (Spline2D.s, ascending from 0), xy [2][4][n-1] (x(s) then y(s); rows a, b, c, d per
@@ -247,6 +278,20 @@ int llampc_bank_set_raceline(llampc_bank* bank, const double* knots, int32_t n, 
  * LLAMPC_SYNC_COMPLETION=1 in the environment selects the copy + synchronise path. */
 int llampc_plan(llampc_bank* bank, const llampc_plan_in* in, llampc_plan_out* out,
                 double* err_out, double* wmean_out, double* cost_out);
+/* llampc_plan with the look-ahead under a corridor (extends llampc_plan; hp, weight and the cost
+ * J_c as llampc_lookahead_corridor): the same blocking tick in ONE launch — the look-back half,
+ * the NaN policies, the selection and the record are llampc_plan's, with J_c in the cost's place.
+ * Both completion modes: outputs copied back, or (err_out, wmean_out and cost_out all NULL) the
+ * record through pinned host memory and its tag.  hp rides behind the other inputs in the bank's
+ * staging buffer (one host-to-device copy; a corridor tick's inputs never travel as kernel
+ * arguments).  LLAMPC_E_ARG, with nothing enqueued and the launch counter unchanged: hp NULL,
+ * do_lookahead 0, LLAMPC_RK6, LLAMPC_XREF_RACELINE, a corridor or weight as above.
+ * Not yet under a corridor (the remaining steps): llampc_plan_async / _wait,
+ * llampc_plan_device, llampc_plan_exchange and the sharded bank, the controller tick
+ * (llampc_ctl_*), the work-queue and inline-pack layouts, RK6, the per-model raceline reference. */
+int llampc_plan_corridor(llampc_bank* bank, const llampc_plan_in* in, const double* hp /* [H][6] */,
+                         double weight, llampc_plan_out* out, double* err_out, double* wmean_out,
+                         double* cost_out);
 /* Host pointers; asynchronous (SURVEY.md §8b "_async" variant): the inputs are copied
  * into the bank's pinned staging buffer before the call returns (the caller may reuse
  * them), and the H2D copy and the plan kernel are enqueued on the bank's stream; the

@@ -67,7 +67,7 @@ static void timing_free(llampc_bank* b) {
 // The tick on device pointers (capi_common.hpp).  Advances the window bookkeeping when a look-back runs.
 int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out, double* d_err, double* d_wmean,
                 double* d_cost, hipStream_t s, uint64_t* host_tag, uint64_t host_seq, const InlinePack* pk,
-                llampc_mailbox* px, llampc_plan_out* px_merged) {
+                llampc_mailbox* px, llampc_plan_out* px_merged, const PlanCorridor* cor) {
   const bool lb = in.do_lookback != 0;
   const bool la = in.do_lookahead != 0;
   const bool raceline = la && in.xref_mode == LLAMPC_XREF_RACELINE;
@@ -158,7 +158,7 @@ int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out
   f.wq = b->d_wq.get();
   {
     TimedLaunch tl(b, 0, s);
-    HIP_TRY(launch_plan(lb ? &lbl : nullptr, la ? &lal : nullptr, f, s, pk, b->share));
+    HIP_TRY(launch_plan(lb ? &lbl : nullptr, la ? &lal : nullptr, f, s, pk, b->share, cor));
   }
   b->seq = seq;
   if (px) px->seq = px_seq;
@@ -179,14 +179,22 @@ bool inline_inputs(const llampc_plan_in* in) {
          getenv("LLAMPC_NO_INLINE") == nullptr;
 }
 
-// Pack a host plan input into the pinned buffer; return a device-pointer copy of `in`.
-int stage_inputs(llampc_bank* b, const llampc_plan_in* in, llampc_plan_in* dev_in, hipStream_t s) {
-  const size_t total = pack_len(in);
+// Pack a host plan input into the pinned buffer; return a device-pointer copy of `in`.  hp (the
+// corridor tick): the half-planes [H][6] ride behind the pack in the same copy, *d_hp their device
+// address.
+int stage_inputs(llampc_bank* b, const llampc_plan_in* in, llampc_plan_in* dev_in, hipStream_t s,
+                 const double* hp = nullptr, const double** d_hp = nullptr) {
+  const size_t len = pack_len(in);
   const int64_t H = in->do_lookahead ? in->H : 0;
+  const size_t total = len + (hp ? 6 * (size_t)H : 0);
   int rc;
   if ((rc = b->h_in.reserve(total, 1024, "input pack", LLAMPC_E_HIP)) || (rc = b->d_in.reserve(total, 1024))) return rc;
   pack_into(in, b->h_in.get());
   double* d = b->d_in.get();
+  if (hp) {
+    std::memcpy(b->h_in.get() + len, hp, 6 * (size_t)H * sizeof(double));
+    *d_hp = d + len;
+  }
   HIP_TRY(hipMemcpyAsync(d, b->h_in.get(), total * sizeof(double), hipMemcpyHostToDevice, s));
   *dev_in = *in;
   dev_in->x_prev = d;
@@ -204,15 +212,18 @@ bool host_completion() { return getenv("LLAMPC_SYNC_COMPLETION") == nullptr; }
 
 // The host-completion tick: the inputs inline or staged, the record into pinned host memory,
 // then tick number *seq into the tag (wait_host_tag).
-int plan_launch_host(llampc_bank* b, const llampc_plan_in* in, hipStream_t s, uint64_t* seq) {
+// hp: the corridor tick, whose inputs are always staged (the corridor rides with them).
+int plan_launch_host(llampc_bank* b, const llampc_plan_in* in, hipStream_t s, uint64_t* seq,
+                     const double* hp = nullptr, double weight = 0.0) {
   llampc_plan_in din = *in;
   InlinePack pk;
-  const bool inl = inline_inputs(in);
+  PlanCorridor cor{nullptr, weight};
+  const bool inl = !hp && inline_inputs(in);
   if (inl) pack_into(in, pk.v);
-  else if (int rc = stage_inputs(b, in, &din, s)) return rc;
+  else if (int rc = stage_inputs(b, in, &din, s, hp, &cor.hp)) return rc;
   *seq = ++b->hseq;
   return plan_launch(b, din, b->host.rec.dev(), nullptr, nullptr, nullptr, s, b->host.tag.dev(), *seq,
-                     inl ? &pk : nullptr);
+                     inl ? &pk : nullptr, nullptr, nullptr, hp ? &cor : nullptr);
 }
 
 // After a tick whose record reports a device-side status (an in-launch wait gave up) or whose
@@ -482,11 +493,28 @@ int llampc_bank_timing_read(llampc_bank* b, double* avg_ms, int64_t* count) {
   return LLAMPC_OK;
 }
 
-int llampc_plan(llampc_bank* b, const llampc_plan_in* in, llampc_plan_out* out, double* err_out,
-                double* wmean_out, double* cost_out) {
+}  // extern "C"
+
+// What a corridor tick refuses before anything is enqueued (llampc_plan_corridor,
+// llampc_lookahead_corridor): no look-ahead, RK6, the per-model raceline reference, a corridor or
+// weight corridor_invalid names.
+static int check_corridor_mode(const llampc_plan_in* in) {
+  if (!in->do_lookahead) return fail(LLAMPC_E_ARG, "the corridor belongs to the look-ahead: do_lookahead is 0");
+  if (in->integrator == LLAMPC_RK6) return fail(LLAMPC_E_ARG, "the corridor look-ahead has no RK6 rollout");
+  if (in->xref_mode == LLAMPC_XREF_RACELINE)
+    return fail(LLAMPC_E_ARG, "the corridor look-ahead takes the given xref only (not LLAMPC_XREF_RACELINE)");
+  return LLAMPC_OK;
+}
+
+// llampc_plan (hp null) and llampc_plan_corridor: the blocking host-pointer tick.
+static int plan_blocking(llampc_bank* b, const llampc_plan_in* in, const double* hp, double weight,
+                         llampc_plan_out* out, double* err_out, double* wmean_out, double* cost_out) {
   if (!b || !out) return fail(LLAMPC_E_ARG, "bank/out is NULL");
-  int rc = check_plan_in(b, in);
-  if (rc) return rc;
+  int rc;
+  if (hp && in && (rc = check_corridor_mode(in))) return rc;   // E_ARG whatever else the bank lacks
+  if ((rc = check_plan_in(b, in))) return rc;
+  if (hp)                                // H is valid from here on
+    if (const char* why = corridor_invalid(hp, in->H, weight)) return fail(LLAMPC_E_ARG, "corridor: %s", why);
   std::lock_guard<std::mutex> lk(b->mu);
   bank_disarm(b);
   if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding: call llampc_plan_wait");
@@ -495,7 +523,7 @@ int llampc_plan(llampc_bank* b, const llampc_plan_in* in, llampc_plan_out* out, 
   if (!err_out && !wmean_out && !cost_out && host_completion()) {
     // the record only: the kernel writes it to pinned host memory and publishes a tag
     uint64_t seq;
-    if ((rc = plan_launch_host(b, in, s, &seq)) || (rc = wait_host_tag(b, seq, out))) return rc;
+    if ((rc = plan_launch_host(b, in, s, &seq, hp, weight)) || (rc = wait_host_tag(b, seq, out))) return rc;
     if (out->status) return status_fail(b, out->status);
     return LLAMPC_OK;
   }
@@ -505,9 +533,11 @@ int llampc_plan(llampc_bank* b, const llampc_plan_in* in, llampc_plan_out* out, 
     d_cost = b->d_cost.get();
   }
   llampc_plan_in din;
-  if ((rc = stage_inputs(b, in, &din, s))) return rc;
+  PlanCorridor cor{nullptr, weight};
+  if ((rc = stage_inputs(b, in, &din, s, hp, &cor.hp))) return rc;
   if ((rc = plan_launch(b, din, b->d_out.get(), err_out ? b->d_err.get() : nullptr,
-                        wmean_out ? b->d_wmean.get() : nullptr, d_cost, s)))
+                        wmean_out ? b->d_wmean.get() : nullptr, d_cost, s, nullptr, 0, nullptr, nullptr, nullptr,
+                        hp ? &cor : nullptr)))
     return rc;
   HIP_TRY(hipMemcpyAsync(b->h_out.get(), b->d_out.get(), sizeof(llampc_plan_out), hipMemcpyDeviceToHost, s));
   if (err_out && in->do_lookback)
@@ -520,6 +550,19 @@ int llampc_plan(llampc_bank* b, const llampc_plan_in* in, llampc_plan_out* out, 
   *out = *b->h_out.get();
   if (out->status) return status_fail(b, out->status);
   return LLAMPC_OK;
+}
+
+extern "C" {
+
+int llampc_plan(llampc_bank* b, const llampc_plan_in* in, llampc_plan_out* out, double* err_out,
+                double* wmean_out, double* cost_out) {
+  return plan_blocking(b, in, nullptr, 0.0, out, err_out, wmean_out, cost_out);
+}
+
+int llampc_plan_corridor(llampc_bank* b, const llampc_plan_in* in, const double* hp, double weight,
+                         llampc_plan_out* out, double* err_out, double* wmean_out, double* cost_out) {
+  if (!hp) return fail(LLAMPC_E_ARG, "hp is NULL (llampc_plan is the tick without a corridor)");
+  return plan_blocking(b, in, hp, weight, out, err_out, wmean_out, cost_out);
 }
 
 int llampc_bank_set_raceline(llampc_bank* b, const double* knots, int32_t n, const double* xy,
@@ -633,10 +676,13 @@ int llampc_lookback(llampc_bank* b, const double* x_prev, const double* u_prev, 
   return LLAMPC_OK;
 }
 
-int llampc_lookahead(llampc_bank* b, const double* x0, const double* U, int32_t C, int32_t H,
-                     const double* xref, const double* uprev, const llampc_cost* cost, double Ts,
-                     int32_t integrator, double* cost_out, int32_t* best_cand_out,
-                     int64_t* best_model, int32_t* best_cand, double* best_cost) {
+}  // extern "C"
+
+// llampc_lookahead (hp null) and llampc_lookahead_corridor.
+static int lookahead_blocking(llampc_bank* b, const double* x0, const double* U, int32_t C, int32_t H,
+                              const double* xref, const double* uprev, const llampc_cost* cost, double Ts,
+                              int32_t integrator, const double* hp, double weight, double* cost_out,
+                              int32_t* best_cand_out, int64_t* best_model, int32_t* best_cand, double* best_cost) {
   if (!cost) return fail(LLAMPC_E_ARG, "cost is NULL");
   llampc_plan_in in{};
   in.x_now = x0;
@@ -653,7 +699,7 @@ int llampc_lookahead(llampc_bank* b, const double* x0, const double* U, int32_t 
   in.Ts = Ts;
   in.cost = *cost;
   llampc_plan_out o;
-  int rc = llampc_plan(b, &in, &o, nullptr, nullptr, cost_out);
+  int rc = plan_blocking(b, &in, hp, weight, &o, nullptr, nullptr, cost_out);
   if (rc) return rc;
   if (best_cand_out) {
     DeviceGuard g(b->device);
@@ -663,6 +709,26 @@ int llampc_lookahead(llampc_bank* b, const double* x0, const double* U, int32_t 
   if (best_cand) *best_cand = o.la_best_cand;
   if (best_cost) *best_cost = o.la_best_cost;
   return LLAMPC_OK;
+}
+
+extern "C" {
+
+int llampc_lookahead(llampc_bank* b, const double* x0, const double* U, int32_t C, int32_t H,
+                     const double* xref, const double* uprev, const llampc_cost* cost, double Ts,
+                     int32_t integrator, double* cost_out, int32_t* best_cand_out,
+                     int64_t* best_model, int32_t* best_cand, double* best_cost) {
+  return lookahead_blocking(b, x0, U, C, H, xref, uprev, cost, Ts, integrator, nullptr, 0.0, cost_out, best_cand_out,
+                            best_model, best_cand, best_cost);
+}
+
+int llampc_lookahead_corridor(llampc_bank* b, const double* x0, const double* U, int32_t C, int32_t H,
+                              const double* xref, const double* uprev, const llampc_cost* cost, double Ts,
+                              int32_t integrator, double* cost_out, int32_t* best_cand_out,
+                              int64_t* best_model, int32_t* best_cand, double* best_cost, const double* hp,
+                              double weight) {
+  if (!hp) return fail(LLAMPC_E_ARG, "hp is NULL (llampc_lookahead is the look-ahead without a corridor)");
+  return lookahead_blocking(b, x0, U, C, H, xref, uprev, cost, Ts, integrator, hp, weight, cost_out, best_cand_out,
+                            best_model, best_cand, best_cost);
 }
 
 int llampc_merge(const llampc_plan_out* parts, int32_t G, int32_t nan_policy, llampc_plan_out* merged) {
@@ -808,6 +874,23 @@ extern "C" int llampc_plan_variant(int64_t n, int32_t C, int32_t H, int32_t inte
   const int G = lookahead_group(C);
   bool stage = false;
   (void)lookahead_lds_bytes(C, H, &stage);
+  out[0] = lookahead_lpm(n, C, integrator, share);
+  out[1] = G;
+  out[2] = (C + G - 1) / G;
+  out[3] = stage ? 1 : 0;
+  return LLAMPC_OK;
+}
+
+// The variant a corridor launch takes (launch_plan with a PlanCorridor): the same functions.
+extern "C" int llampc_plan_variant_corridor(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share,
+                                            int32_t out[4]) {
+  if (!out) return fail(LLAMPC_E_ARG, "NULL argument");
+  if (n < 1 || C < 1 || H < 1 || (integrator != LLAMPC_RK4 && integrator != LLAMPC_EULER_NLP))
+    return fail(LLAMPC_E_ARG, "n %lld, C %d, H %d, integrator %d (the corridor look-ahead: RK4 or NLP-Euler)",
+                (long long)n, C, H, integrator);
+  const int G = lookahead_group(C);
+  bool stage = false;
+  (void)lookahead_lds_bytes_corridor(C, H, &stage);
   out[0] = lookahead_lpm(n, C, integrator, share);
   out[1] = G;
   out[2] = (C + G - 1) / G;

@@ -212,11 +212,12 @@ void bank_disarm(llampc_bank* b);
 int bank_dedicate(llampc_bank* b);
 int check_plan_in(const llampc_bank* b, const llampc_plan_in* in);
 // The tick on device pointers: ONE launch (look-back + look-ahead + completion).  host_tag:
-// host completion; pk: the inputs as kernel arguments; px: the fused peer exchange.
+// host completion; pk: the inputs as kernel arguments; px: the fused peer exchange; cor: the
+// look-ahead's corridor (device half-planes and weight; never with pk or px).
 int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out, double* d_err, double* d_wmean,
                 double* d_cost, hipStream_t s, uint64_t* host_tag = nullptr, uint64_t host_seq = 0,
                 const llampc::InlinePack* pk = nullptr, llampc_mailbox* px = nullptr,
-                llampc_plan_out* px_merged = nullptr);
+                llampc_plan_out* px_merged = nullptr, const llampc::PlanCorridor* cor = nullptr);
 inline hipStream_t pick_stream(llampc_bank* b, void* s) { return s ? (hipStream_t)s : b->stream; }
 
 // llampc_nlp_create's checks of a cfg (capi_nlp.hip), llampc_nlp_batch_create's too.

@@ -320,6 +320,15 @@ size_t lookahead_lds_bytes(int32_t C, int32_t H, bool* stage_u) {
   return *stage_u ? base + ub : base;
 }
 
+// The corridor launch: hp [H][6] (48 H bytes) behind the staged inputs; a shape whose inputs no
+// longer fit beside it goes unstaged.
+size_t lookahead_lds_bytes_corridor(int32_t C, int32_t H, bool* stage_u) {
+  const size_t base = kScratchBytes + 16 * (size_t)(H + 1) + 48 * (size_t)H;
+  const size_t ub = 8 * kStageW * (size_t)C * H;
+  *stage_u = base + ub <= kStageLimit;
+  return *stage_u ? base + ub : base;
+}
+
 // Models per look-back lane: keep the block lists small enough for the in-LDS tree merge
 // (nb_lb * K <= 640 entries = 20 KB for both buffers).
 // Models per lane: lb_final holds blocks * kWaves * K entries in LDS and merges at most
@@ -362,7 +371,11 @@ static int device_cus() {
 }
 
 hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, FinalLaunch f,
-                       hipStream_t s, const InlinePack* pk, int32_t share) {
+                       hipStream_t s, const InlinePack* pk, int32_t share, const PlanCorridor* cor) {
+  // the corridor launch: RK4 or NLP-Euler on the shared xref, device inputs, no peer exchange
+  if (cor && (!la || !cor->hp || pk || f.px_G || la->xref_mode != LLAMPC_XREF_GIVEN ||
+              (la->integrator != LLAMPC_RK4 && la->integrator != LLAMPC_EULER_NLP)))
+    return hipErrorInvalidValue;
   LookbackLaunch lbv{};
   LookaheadLaunch lav{};
   int G = 1, cpl = 1, lpm = 1, integ = LLAMPC_RK4;
@@ -405,6 +418,8 @@ hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, Fina
       const size_t room = base + rl < kLdsMax ? kLdsMax - base - rl : 0;
       lav.rl.wcap = (int32_t)std::min<size_t>(room / per_seg, (size_t)(la->rl.n - 1));
       lds = std::max(lds, base + rl + per_seg * (size_t)lav.rl.wcap);
+    } else if (cor) {
+      lds = std::max(lds, lookahead_lds_bytes_corridor(la->C, la->H, &stage));
     } else {
       lds = std::max(lds, lookahead_lds_bytes(la->C, la->H, &stage));
     }
@@ -425,7 +440,7 @@ hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, Fina
   // LLAMPC_WQ_WAVES=4|8 forces a work-queue block size (A/B runs).
   int wq = 0;
   if (la && la->wq && lpm == 1 && G <= 64 && integ == LLAMPC_RK4 && la->xref_mode == LLAMPC_XREF_GIVEN &&
-      !pk && getenv("LLAMPC_NO_WQ") == nullptr) {
+      !pk && !cor && getenv("LLAMPC_NO_WQ") == nullptr) {
     const int nw = std::max(1, device_cus() - 1);
     const char* force = getenv("LLAMPC_WQ_WAVES");
     const int forced = force ? atoi(force) : 0;
@@ -448,6 +463,13 @@ hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, Fina
     if (lpm == 4) launch_plan_inline_group<4>(lbv, lav, f, G, cpl, lds, s, *pk);
     else if (lpm == 2) launch_plan_inline_group<2>(lbv, lav, f, G, cpl, lds, s, *pk);
     else launch_plan_inline_group<1>(lbv, lav, f, G, cpl, lds, s, *pk);
+    return hipGetLastError();
+  }
+  if (cor) {                             // block per models, the unsplit rollouts (plan_kernel_corr)
+    const bool rk4 = integ == LLAMPC_RK4;
+    if (lpm == 4) (rk4 ? launch_plan_corridor_group<0, 4> : launch_plan_corridor_group<1, 4>)(lbv, lav, f, G, cpl, stage, lds, s, *cor);
+    else if (lpm == 2) (rk4 ? launch_plan_corridor_group<0, 2> : launch_plan_corridor_group<1, 2>)(lbv, lav, f, G, cpl, stage, lds, s, *cor);
+    else (rk4 ? launch_plan_corridor_group<0, 1> : launch_plan_corridor_group<1, 1>)(lbv, lav, f, G, cpl, stage, lds, s, *cor);
     return hipGetLastError();
   }
   switch (integ) {

@@ -121,6 +121,16 @@ struct InlinePack {
   double v[kInlineDoubles];
 };
 
+// The look-ahead's corridor (llampc_plan_corridor, llampc_lookahead_corridor): the plan kernel's own
+// trailing argument, as NlpCorridor is nlp_kernel's, so the launch structs above keep their layout.
+// hp [H][6] (device): per step k = 1..H the half-planes (a0, a1, b, c0, c1, d), a.p_k <= b and
+// c.p_k <= d on the position after k steps of the launch's integrator; every (model, candidate)
+// cost becomes J + weight x the summed squared slacks (rollout_dev.hpp kRCorr).
+struct PlanCorridor {
+  const double* hp;
+  double weight;
+};
+
 int lookback_blocks(int64_t n);
 int lookahead_group(int32_t C);
 int lookahead_lpm(int64_t n, int32_t C, int32_t integrator, int32_t share = 1);
@@ -128,14 +138,20 @@ int lookahead_blocks(int64_t n, int32_t C, int lpm);
 int lookback_r(int64_t n, int32_t K);               // models per look-back lane
 int lookback_blocks_r(int64_t n, int R);
 size_t lookahead_lds_bytes(int32_t C, int32_t H, bool* stage_u);
+// ... of a corridor launch: hp [H][6] behind the staged inputs, which stay staged only if both fit
+size_t lookahead_lds_bytes_corridor(int32_t C, int32_t H, bool* stage_u);
 size_t raceline_lds_bytes(int32_t n, int32_t M);
 
 // The whole tick in ONE launch: look-back blocks (if lb), look-ahead blocks (if la), and
 // the completion stages run by ticket winners; writes f.out.  f.nb_* / f.do_* are set here.
 // pk != null: the inputs are in *pk (see InlinePack); needs a look-ahead with RK4, the
 // given xref and U staged in LDS (plan_inline_ok), else hipErrorInvalidValue.
+// cor != null: the corridor launch (plan_kernel_corr) — block per models on the unsplit rollouts,
+// never the work queue, the inline pack or the fused peer exchange; hipErrorInvalidValue, with
+// nothing enqueued, for RK6, the raceline reference, pk or a peer exchange (f.px_G).
 hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, FinalLaunch f,
-                       hipStream_t s, const InlinePack* pk = nullptr, int32_t share = 1);
+                       hipStream_t s, const InlinePack* pk = nullptr, int32_t share = 1,
+                       const PlanCorridor* cor = nullptr);
 bool plan_inline_ok(int32_t C, int32_t H, int32_t integrator, int32_t xref_mode);
 // The plan-kernel variant groups (plan_dev.hpp; one translation unit per group, plan_*.hip):
 // (integrator, lanes per rollout) with the staged / unstaged inputs and, for RK4 at LPM 1, the
@@ -157,6 +173,19 @@ LLAMPC_PLAN_GROUP_DECL(1, 4);
 LLAMPC_PLAN_GROUP_DECL(1, 2);
 LLAMPC_PLAN_GROUP_DECL(1, 1);
 LLAMPC_PLAN_GROUP_DECL(2, 1);
+template <int INTEG, int LPM>
+void launch_plan_corridor_group(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f, int G,
+                                int cpl, bool stage, size_t lds, hipStream_t s, const PlanCorridor& cor);
+#define LLAMPC_PLAN_CORRIDOR_GROUP_DECL(I, L)                                                               \
+  extern template void launch_plan_corridor_group<I, L>(const LookbackLaunch&, const LookaheadLaunch&,      \
+                                                        const FinalLaunch&, int, int, bool, size_t,          \
+                                                        hipStream_t, const PlanCorridor&)
+LLAMPC_PLAN_CORRIDOR_GROUP_DECL(0, 4);
+LLAMPC_PLAN_CORRIDOR_GROUP_DECL(0, 2);
+LLAMPC_PLAN_CORRIDOR_GROUP_DECL(0, 1);
+LLAMPC_PLAN_CORRIDOR_GROUP_DECL(1, 4);
+LLAMPC_PLAN_CORRIDOR_GROUP_DECL(1, 2);
+LLAMPC_PLAN_CORRIDOR_GROUP_DECL(1, 1);
 extern template void launch_plan_inline_group<4>(const LookbackLaunch&, const LookaheadLaunch&, const FinalLaunch&,
                                                  int, int, size_t, hipStream_t, const InlinePack&);
 extern template void launch_plan_inline_group<2>(const LookbackLaunch&, const LookaheadLaunch&, const FinalLaunch&,

@@ -66,14 +66,22 @@ __device__ __forceinline__ void la_publish(const LookaheadLaunch& a, int blk, co
 // bank's work counter, so the staging prologue runs once per CU instead of once per 4 models
 // and no CU waits for a new block between units (v29 stamps at C = 64: prologue 3.4 us and
 // reduction 2 us of each 45 us block).
-template <int INTEG, bool STAGE, int LPM, int XM, int WQ = 0>
+// CORR (the corridor look-ahead, plan_kernel_corr): the half-planes ghp [H][6] (global) are copied
+// to LDS behind the staged inputs — loaded with the prologue's other inputs, stored ahead of its
+// barrier — and every rollout adds cw times its summed squared slacks (rollout_dev.hpp kRCorr) on the
+// unsplit rollout; a block-per-models launch on the shared xref only.
+template <int INTEG, bool STAGE, int LPM, int XM, int WQ = 0, bool CORR = false>
 __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int blk, int G, int cpl,
-                                                unsigned char* smem, const Scratch& sc) {
+                                                unsigned char* smem, const Scratch& sc,
+                                                const double* ghp = nullptr, double cw = 0.0) {
+  static_assert(!CORR || (!XM && !WQ && INTEG != 2), "corridor look-ahead: shared xref, block per models, RK4 or NLP-Euler");
   LA_STAMP(blk, 0);
   constexpr int BT = wq_threads(WQ);   // threads of this block
   double* sx = reinterpret_cast<double*>(smem + kScratchBytes);
   double* su = sx + 2 * (a.H + 1);
   const int H = a.H, C = a.C;
+  double* shp = nullptr;               // CORR: hp [H][6] after the staged inputs (16-B aligned rows)
+  if constexpr (CORR) shp = su + (STAGE ? kStageW * C * H : 0);
   // this lane's model: its Pacejka row and the start state are loaded first, so they are in
   // flight while the block stages the shared inputs (one HBM round trip, not two)
   const int sub = threadIdx.x % LPM;
@@ -338,6 +346,14 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
     };
     double sua = 0.0, sdl = 0.0, sp0 = 0.0, sp1 = 0.0;
     if (STAGE) stage_load(tid, sua, sdl, sp0, sp1);
+    // CORR: this thread's two corridor elements (6 H <= 2 BT up to H = 85; the rest, if any, in a
+    // plain loop below), clamped like the other loads
+    [[maybe_unused]] double hv0 = 0.0, hv1 = 0.0;
+    if constexpr (CORR) {
+      const int nh = 6 * H;
+      hv0 = ghp[tid < nh ? tid : nh - 1];
+      hv1 = ghp[tid + BT < nh ? tid + BT : nh - 1];
+    }
     // under the loads' latency: the polynomial constants, the pins, this lane's model
     K0 = load_la_consts<INTEG, LPM>();
     pin_consts();
@@ -374,6 +390,13 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
     // a lane past the reference's or the staging's end never reads its clamped loads: without
     // this use the wait for them lands in the rollout loop, where their registers are reused
     asm volatile("" ::"v"(xr0), "v"(xr1), "v"(sua), "v"(sdl), "v"(sp0), "v"(sp1));
+    if constexpr (CORR) {
+      const int nh = 6 * H;
+      if (tid < nh) shp[tid] = hv0;
+      if (tid + BT < nh) shp[tid + BT] = hv1;
+      for (int e = tid + 2 * BT; e < nh; e += BT) shp[e] = ghp[e];
+      asm volatile("" ::"v"(hv0), "v"(hv1));
+    }
     __syncthreads();
   }
 
@@ -517,7 +540,10 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
       if (c >= C) break;
       bool bad = false;
       double J;
-      if (kSplit && diagQP)             // launch-uniform (kernel arguments)
+      if constexpr (CORR)               // the unsplit rollout whatever Q and P: the lane needs X and Y
+        J = rollout<INTEG, LPM, kRF | kRFast | kRCorr>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, bad,
+                                                       nullptr, nullptr, nullptr, 0, nullptr, shp, cw);
+      else if (kSplit && diagQP)        // launch-uniform (kernel arguments)
         J = rollout<INTEG, LPM, kRF | kRFast | kRSplitQ>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, bad);
       else
         J = rollout<INTEG, LPM, kRF | kRFast>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, bad);
@@ -535,7 +561,12 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
       }
       if (__builtin_expect(__any(bad), 0)) {
         bool unused = false;
-        if (bad) J = rollout<INTEG, LPM, kRF>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, unused);
+        if constexpr (CORR) {
+          if (bad) J = rollout<INTEG, LPM, kRF | kRCorr>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, unused,
+                                                         nullptr, nullptr, nullptr, 0, nullptr, shp, cw);
+        } else {
+          if (bad) J = rollout<INTEG, LPM, kRF>(a, c, n, x0, sx, su, veh, t, sk, q, Ts, up0, up1, K, fq, unused);
+        }
       }
       if (sub == 0) {
         if (a.cost_out) a.cost_out[n * C + c] = J;

@@ -19,9 +19,10 @@ namespace llampc {
 // (lb_final) while look-ahead blocks still run; the last block overall completes the
 // llampc_plan_out record (final_select).
 // ------------------------------------------------------------------------------------
-template <int INTEG, bool STAGE, int LPM, int XM, bool PX = false, int WQ = 0>
+template <int INTEG, bool STAGE, int LPM, int XM, bool PX = false, int WQ = 0, bool CORR = false>
 __device__ __forceinline__ void plan_body(const LookbackLaunch& lb, const LookaheadLaunch& la,
-                                          const FinalLaunch& fin, int G, int cpl) {
+                                          const FinalLaunch& fin, int G, int cpl,
+                                          const double* hp = nullptr, double cw = 0.0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const Scratch sc(smem);
   int* flag = reinterpret_cast<int*>(smem + kFlagOff);
@@ -51,7 +52,8 @@ __device__ __forceinline__ void plan_body(const LookbackLaunch& lb, const Lookah
       return;
     }
   } else {
-    lookahead_block<INTEG, STAGE, LPM, XM, WQ>(la, la_blk, G, cpl, smem, sc);
+    if constexpr (CORR) lookahead_block<INTEG, STAGE, LPM, XM, WQ, true>(la, la_blk, G, cpl, smem, sc, hp, cw);
+    else lookahead_block<INTEG, STAGE, LPM, XM, WQ>(la, la_blk, G, cpl, smem, sc);
     if (fin.poll) return;                // published tagged records; no ticket
     if constexpr (wq_threads(WQ) > kBlock) {
       if (threadIdx.x >= kBlock) return;
@@ -108,6 +110,20 @@ __global__ __launch_bounds__(kBlock) void plan_kernel_inl(LookbackLaunch, Lookah
   la.U = v + 16 + 2 * (la.H + 1);
   plan_body<0, true, LPM, 0>(lb, la, kernarg_at<FinalLaunch>(kp, kArgFin), kernarg_at<int>(kp, kArgG),
                              kernarg_at<int>(kp, kArgG + 4));
+}
+
+// The corridor tick (llampc_plan_corridor, llampc_lookahead_corridor): the same launch with the
+// corridor as its own trailing argument (PlanCorridor, kernels.hpp), so the three launch structs and
+// every other plan kernel keep their layout and code.  Shared xref, block per models, no peer
+// exchange; the look-ahead blocks take the unsplit rollouts with the corridor term
+// (lookahead_block CORR).  The corridor is read by value: two scalar loads behind the touch.
+template <int INTEG, bool STAGE, int LPM>
+__global__ __launch_bounds__(kBlock) void plan_kernel_corr(LookbackLaunch, LookaheadLaunch, FinalLaunch, int, int,
+                                                           PlanCorridor cor) {
+  const KernargPtr kp = touch_kernargs<kPlanArgBytes>();
+  plan_body<INTEG, STAGE, LPM, 0, false, 0, true>(kernarg_at<LookbackLaunch>(kp, 0), kernarg_at<LookaheadLaunch>(kp, kArgLa),
+                                                  kernarg_at<FinalLaunch>(kp, kArgFin), kernarg_at<int>(kp, kArgG),
+                                                  kernarg_at<int>(kp, kArgG + 4), cor.hp, cor.weight);
 }
 
 constexpr size_t kOneBlockPerCuLds = 82 * 1024;
@@ -179,6 +195,24 @@ template <int LPM>
 void launch_plan_inline_group(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f,
                               int G, int cpl, size_t lds, hipStream_t s, const InlinePack& pk) {
   launch_plan_inl<LPM>(lb, la, f, G, cpl, lds, s, pk);
+}
+
+template <int INTEG, bool STAGE, int LPM>
+static void launch_plan_corr(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f, int G,
+                             int cpl, size_t lds, hipStream_t s, const PlanCorridor& cor) {
+  lds = std::max(lds, kOneBlockPerCuLds);
+  allow_lds(plan_kernel_corr<INTEG, STAGE, LPM>);
+  hipLaunchKernelGGL((plan_kernel_corr<INTEG, STAGE, LPM>), dim3(f.nb_lb + f.nb_la), dim3(kBlock), lds, s, lb, la, f,
+                     G, cpl, cor);
+}
+
+// The corridor launch's variant group: (integrator, lanes per rollout), staged or not; explicitly
+// instantiated in plan_corr_*.hip (declared extern in kernels.hpp).
+template <int INTEG, int LPM>
+void launch_plan_corridor_group(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f, int G,
+                                int cpl, bool stage, size_t lds, hipStream_t s, const PlanCorridor& cor) {
+  if (stage) launch_plan_corr<INTEG, true, LPM>(lb, la, f, G, cpl, lds, s, cor);
+  else launch_plan_corr<INTEG, false, LPM>(lb, la, f, G, cpl, lds, s, cor);
 }
 
 }  // namespace llampc

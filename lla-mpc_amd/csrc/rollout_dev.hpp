@@ -83,8 +83,9 @@ enum RolloutFlag : unsigned {
   kRTraj = 1u << 5,   // TRAJ: the state after every step to `traj` (three 16-B stores; null: none)
   kRS4 = 1u << 6,     // S4 (ctl_cand_dev.hpp ctl_stage, with ULDS and FAST): sin / cos delta and the cost terms read at `s4`
   kRDefer = 1u << 7,  // DEFER (ctl_spec_dev.hpp ctl_spec, with SPLIT and S4): positions to `dpos`, the rest to *dout
-  kRCorr = 1u << 8,   // CORR (nlp.hip's corridor solve): two position half-planes per step at `hp` [H][6] (LDS), the
-                      //   squared slacks summed over the horizon, J + cw pen (corridor_slack2 below)
+  kRCorr = 1u << 8,   // CORR (nlp.hip's corridor solve, the plan kernel's corridor look-ahead): two position half-planes
+                      //   per step at `hp` [H][6] (LDS), the squared slacks summed over the horizon, J + cw pen
+                      //   (corridor_slack2 above); unsplit rollouts only, fused RK4 or NLP-Euler at any LPM
   kRQuadr = 1u << 9,  // QUADR (with SPLIT; the plan kernel's lookahead_block): the component is a per-step quadrature in
                       //   quad lanes 2 / 3 (dyn.hpp step_fused kPosQuadr), no position broadcast in the stages; lanes 0 / 1
                       //   hold garbage in x[0] and track, J = (J_X + J_Y) + act from lanes 2 and 3
@@ -124,7 +125,7 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
   static_assert(!QUADR || (SPLIT && !DEFER), "position quadrature: a split rollout that forms its own tracking term");
   static_assert(!ULDS || !STAGE, "candidates in LDS: unstaged rollout");
   static_assert(!CORR || (!SPLIT && !DEFER), "corridor term: a lane that holds both position components");
-  static_assert(!CORR || (INTEG == 1 && LPM == 4 && !S4 && !XM), "corridor term: built for the NLP kernel's rollouts");
+  static_assert(!CORR || (INTEG != 2 && !S4 && !XM), "corridor term: the NLP kernel's and the plan kernel's shared-xref rollouts");
   const int H = a.H, C = a.C;
   const double* Ub = ULDS ? su : a.U;
   double x[6];

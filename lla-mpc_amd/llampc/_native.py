@@ -129,7 +129,17 @@ _SIGNATURES = {
                                    C.POINTER(C.c_int32), _dp]),
     "llampc_plan_variant": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(C.c_int32)]),
+    # llampc_lookahead's, then hp [H][6], weight
+    "llampc_lookahead_corridor": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp,
+                                            C.POINTER(Cost), C.c_double, C.c_int32, _dp,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int32), _dp, _dp, C.c_double]),
+    "llampc_plan_variant_corridor": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(C.c_int32)]),
     "llampc_plan": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), C.POINTER(PlanOut), _dp, _dp, _dp]),
+    # bank, in, hp [H][6], weight, then llampc_plan's outputs
+    "llampc_plan_corridor": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), _dp, C.c_double, C.POINTER(PlanOut),
+                                       _dp, _dp, _dp]),
     "llampc_plan_device": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "llampc_merge": (C.c_int, [C.POINTER(PlanOut), C.c_int32, C.c_int32, C.POINTER(PlanOut)]),
@@ -256,6 +266,15 @@ def plan_variant(n: int, C_: int, H: int, integrator="rk4", share: int = 1) -> d
     out = (C.c_int32 * 4)()
     integ = INTEGRATORS[integrator] if isinstance(integrator, str) else int(integrator)
     check(load().llampc_plan_variant(int(n), int(C_), int(H), integ, int(share), out))
+    return dict(lpm=out[0], G=out[1], cpl=out[2], stage=bool(out[3]))
+
+
+def plan_variant_corridor(n: int, C_: int, H: int, integrator="rk4", share: int = 1) -> dict:
+    """The variant a corridor launch takes (llampc_plan_variant_corridor; host only, reads LLAMPC_LPM
+    as the launch does): {lpm, G, cpl, stage}, stage counting the corridor's own LDS."""
+    out = (C.c_int32 * 4)()
+    integ = INTEGRATORS[integrator] if isinstance(integrator, str) else int(integrator)
+    check(load().llampc_plan_variant_corridor(int(n), int(C_), int(H), integ, int(share), out))
     return dict(lpm=out[0], G=out[1], cpl=out[2], stage=bool(out[3]))
 
 

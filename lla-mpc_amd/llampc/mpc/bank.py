@@ -63,6 +63,24 @@ def _pin_template() -> "nat.PlanIn":
 _PIN_TEMPLATE = _pin_template()
 
 
+def check_corridor(corridor, weight, H, integrator="rk4", raceline_start=None):
+    """A look-ahead corridor as the library takes it (llampc_lookahead_corridor, llampc_plan_corridor):
+    -> (hp [H, 6] C-contiguous float64, weight), checked before the library is touched.  ValueError:
+    a shape other than [H, 6], a weight negative or non-finite, integrator "rk6", a corridor together
+    with raceline_start (the per-model reference)."""
+    hp = np.ascontiguousarray(corridor, dtype=np.float64)
+    if hp.shape != (H, 6):
+        raise ValueError(f"corridor must be [H, 6] = {(H, 6)}, got {hp.shape}")
+    weight = float(weight)
+    if not (np.isfinite(weight) and weight >= 0):
+        raise ValueError("corridor_weight must be finite and >= 0")
+    if integrator == "rk6":
+        raise ValueError("the corridor look-ahead has no rk6 rollout: integrator must be 'rk4' or 'euler_nlp'")
+    if raceline_start is not None:
+        raise ValueError("corridor and raceline_start cannot be combined: the corridor look-ahead takes the shared xref")
+    return hp, weight
+
+
 class ModelBank:
     """A shard of the model bank resident on one HIP device."""
 
@@ -184,9 +202,12 @@ class ModelBank:
                     errors=err, window_mean=wm if full else None)
 
     def lookahead(self, x0, U, xref, uprev, Ts=0.02, cost=None, integrator="rk4",
-                  return_costs=False, return_best_cand=False) -> dict:
+                  return_costs=False, return_best_cand=False, corridor=None, corridor_weight=1e4) -> dict:
         """Roll every (model, candidate) over H steps and evaluate the NLP objective
-        (model.py:32-40 x H + nmpc.py:44-111).  U [C, H, 2]; xref [2, H+1]."""
+        (model.py:32-40 x H + nmpc.py:44-111).  U [C, H, 2]; xref [2, H+1].
+        corridor: None, or the half-planes hp [H, 6] of llampc.mpc.constraints (row k - 1 =
+        (a0, a1, b, c0, c1, d) on the position after k steps): every cost gains corridor_weight x the
+        summed squared slacks (llampc_lookahead_corridor; 'rk4' and 'euler_nlp')."""
         U = nat.f64(U)
         if U.ndim == 2:
             U = U.reshape(1, *U.shape)
@@ -194,15 +215,20 @@ class ModelBank:
         xref = nat.f64(xref)
         if xref.shape != (2, H + 1):
             raise ValueError(f"xref must be [2, {H + 1}], got {xref.shape}")
+        if corridor is not None:
+            corridor, corridor_weight = check_corridor(corridor, corridor_weight, H, integrator)
         cost = cost if cost is not None else nat.cost_struct()
         costs = np.empty((self.n, C_)) if return_costs else None
         bc = np.empty(self.n, dtype=np.int32) if return_best_cand else None
         bm, bcand, bcost = nat.C.c_int64(), nat.C.c_int32(), nat.C.c_double()
-        nat.check(nat.load().llampc_lookahead(
-            self.handle, nat.dptr(nat.f64(x0)), nat.dptr(U), C_, H, nat.dptr(xref),
-            nat.dptr(nat.f64(uprev)), nat.C.byref(cost), float(Ts), nat.INTEGRATORS[integrator],
-            nat.dptr(costs), None if bc is None else bc.ctypes.data_as(nat.C.POINTER(nat.C.c_int32)),
-            nat.C.byref(bm), nat.C.byref(bcand), nat.C.byref(bcost)))
+        args = (self.handle, nat.dptr(nat.f64(x0)), nat.dptr(U), C_, H, nat.dptr(xref),
+                nat.dptr(nat.f64(uprev)), nat.C.byref(cost), float(Ts), nat.INTEGRATORS[integrator],
+                nat.dptr(costs), None if bc is None else bc.ctypes.data_as(nat.C.POINTER(nat.C.c_int32)),
+                nat.C.byref(bm), nat.C.byref(bcand), nat.C.byref(bcost))
+        if corridor is None:
+            nat.check(nat.load().llampc_lookahead(*args))
+        else:
+            nat.check(nat.load().llampc_lookahead_corridor(*args, nat.dptr(corridor), corridor_weight))
         return dict(best_model=bm.value, best_cand=bcand.value, best_cost=bcost.value, costs=costs,
                     best_cand_per_model=bc)
 
@@ -260,8 +286,14 @@ class ModelBank:
     def plan_raw(self, x_prev, u_prev, x_now, U, xref, uprev, Ts=0.02, K=10, integrator="rk4",
                  do_lookback=True, do_lookahead=True, current_model=0, nan_policy=nat.NAN_FIRST,
                  cost=None, return_errors=False, return_window_mean=False, return_costs=False,
-                 raceline_start=None):
-        """The fused tick (llampc_plan): returns (PlanOut, errors, window_mean, costs)."""
+                 raceline_start=None, corridor=None, corridor_weight=1e4):
+        """The fused tick (llampc_plan): returns (PlanOut, errors, window_mean, costs).
+        corridor: None, or hp [H, 6] as in lookahead() — the look-ahead half under the corridor
+        (llampc_plan_corridor), everything else of the tick unchanged."""
+        if corridor is not None:
+            Ush = np.shape(U)
+            corridor, corridor_weight = check_corridor(corridor, corridor_weight, Ush[-2] if len(Ush) >= 2 else -1,
+                                                       integrator, raceline_start)
         pin, keep = self._plan_in(x_prev, u_prev, x_now, U, xref, uprev, Ts, K, integrator,
                                   do_lookback, do_lookahead, current_model, nan_policy, cost,
                                   raceline_start)
@@ -270,8 +302,13 @@ class ModelBank:
         wm = np.empty(self.n) if return_window_mean else None
         costs = np.empty((self.n, C_)) if return_costs else None
         out = nat.PlanOut()
-        nat.check(nat.load().llampc_plan(self.handle, nat.C.byref(pin), nat.C.byref(out), nat.dptr(err),
-                                         nat.dptr(wm), nat.dptr(costs)))
+        if corridor is None:
+            nat.check(nat.load().llampc_plan(self.handle, nat.C.byref(pin), nat.C.byref(out), nat.dptr(err),
+                                             nat.dptr(wm), nat.dptr(costs)))
+        else:
+            nat.check(nat.load().llampc_plan_corridor(self.handle, nat.C.byref(pin), nat.dptr(corridor),
+                                                      corridor_weight, nat.C.byref(out), nat.dptr(err),
+                                                      nat.dptr(wm), nat.dptr(costs)))
         return out, err, wm, costs
 
     def plan_async(self, x_prev, u_prev, x_now, U, xref, uprev, Ts=0.02, K=10, integrator="rk4",

@@ -32,11 +32,13 @@ one() {
 export -f one mkvar
 export CSRC DEFS BUNDLER HIPCC
 SRCS=$(mkvar "$ROOT" SRCS)
-for f in $SRCS; do printf '%s\n' "$ROOT $OUT/new $f" "$REF $OUT/old $f"; done |
+# a translation unit the revision does not have is reported as NEW, not compared
+for f in $SRCS; do printf '%s\n' "$ROOT $OUT/new $f"; [ -f "$REF/$CSRC/$f" ] && printf '%s\n' "$REF $OUT/old $f"; done |
   xargs -P 12 -L 1 bash -c 'one "$@" || echo "compile failed: $*" >&2' _
 
 rc=0
 for f in $SRCS; do
-  if cmp -s "$OUT/new/$f.co" "$OUT/old/$f.co"; then echo "IDENTICAL $f"; else echo "DIFFERS   $f"; rc=1; fi
+  if [ ! -f "$REF/$CSRC/$f" ]; then echo "NEW       $f"
+  elif cmp -s "$OUT/new/$f.co" "$OUT/old/$f.co"; then echo "IDENTICAL $f"; else echo "DIFFERS   $f"; rc=1; fi
 done
 exit $rc
