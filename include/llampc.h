@@ -227,7 +227,8 @@ int llampc_lookahead(llampc_bank* bank, const double* x0, const double* U, int32
                      int32_t* best_cand, double* best_cost);
 
 /* The look-ahead kernel variant a launch of n models, C candidates, H steps takes with the
- * shared (GIVEN) xref — host only, no device needed (for tests that mean to run one variant):
+ * shared (GIVEN) xref — host only, no device needed (for tests that mean to run one variant),
+ * from the launch's own rule (plan_shape):
  * out = {lpm (lanes per rollout: 4, 2 or 1; honours the LLAMPC_LPM override exactly as the
  * launch does), G (lanes per model), cpl (candidates per lane), stage (1: the candidate
  * inputs are staged in LDS)}.  share = llampc_bank_set_concurrency's banks (1 by default). */
@@ -256,7 +257,7 @@ int llampc_lookahead_corridor(llampc_bank* bank, const double* x0, const double*
                               int32_t* best_cand, double* best_cost,
                               const double* hp /* [H][6] */, double weight);
 /* llampc_plan_variant for a corridor launch (llampc_lookahead_corridor, llampc_plan_corridor) —
- * host only, from the functions the launch calls: out = {lpm, G, cpl, stage}; stage counts the
+ * host only, from the same rule with a corridor offered: out = {lpm, G, cpl, stage}; stage counts the
  * corridor's 48 H bytes of LDS, so a shape llampc_plan_variant reports staged may be unstaged
  * here.  LLAMPC_E_ARG also for LLAMPC_RK6. */
 int llampc_plan_variant_corridor(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share,

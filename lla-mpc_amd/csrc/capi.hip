@@ -172,10 +172,27 @@ int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out
 
 namespace {
 
-// Host ticks whose inputs travel as kernel arguments (InlinePack): no H2D copy.
-// LLAMPC_NO_INLINE=1 keeps the copy (A/B runs).
+// plan_shape of a look-ahead alone, for what no bank decides: of n models (they matter to the LPM
+// only; a plan input's own questions take n = 1), with the inline pack or a corridor offered.
+PlanShape lookahead_shape(int64_t n, bool la, int32_t C, int32_t H, int32_t integrator, int32_t xref_mode,
+                          int32_t share, bool pack, bool corridor) {
+  PlanShapeIn s{};
+  s.n = n;
+  s.la = la;
+  s.C = C;
+  s.H = H;
+  s.integrator = integrator;
+  s.xref_mode = xref_mode;
+  s.share = share;
+  s.pack = pack;
+  s.corridor = corridor;
+  return plan_shape(s, 0);
+}
+
+// Host ticks whose inputs travel as kernel arguments (InlinePack): no H2D copy — every tick whose
+// launch plan_shape accepts with the pack.  LLAMPC_NO_INLINE=1 keeps the copy (A/B runs).
 bool inline_inputs(const llampc_plan_in* in) {
-  return in->do_lookahead && plan_inline_ok(in->C, in->H, in->integrator, in->xref_mode) &&
+  return !lookahead_shape(1, in->do_lookahead != 0, in->C, in->H, in->integrator, in->xref_mode, 1, true, false).refuse &&
          getenv("LLAMPC_NO_INLINE") == nullptr;
 }
 
@@ -496,13 +513,14 @@ int llampc_bank_timing_read(llampc_bank* b, double* avg_ms, int64_t* count) {
 }  // extern "C"
 
 // What a corridor tick refuses before anything is enqueued (llampc_plan_corridor,
-// llampc_lookahead_corridor): no look-ahead, RK6, the per-model raceline reference, a corridor or
-// weight corridor_invalid names.
+// llampc_lookahead_corridor): no look-ahead, RK6, the per-model raceline reference — plan_shape's
+// refusals of the corridor's modes, in its words (the rest of the input is check_plan_in's to
+// judge) — then a corridor or weight corridor_invalid names.
 static int check_corridor_mode(const llampc_plan_in* in) {
-  if (!in->do_lookahead) return fail(LLAMPC_E_ARG, "the corridor belongs to the look-ahead: do_lookahead is 0");
-  if (in->integrator == LLAMPC_RK6) return fail(LLAMPC_E_ARG, "the corridor look-ahead has no RK6 rollout");
-  if (in->xref_mode == LLAMPC_XREF_RACELINE)
-    return fail(LLAMPC_E_ARG, "the corridor look-ahead takes the given xref only (not LLAMPC_XREF_RACELINE)");
+  const char* why =
+      lookahead_shape(1, in->do_lookahead != 0, in->C, in->H, in->integrator, in->xref_mode, 1, false, true).refuse;
+  if (why == kNoCorridorLookahead || why == kNoCorridorRk6 || why == kNoCorridorRaceline)
+    return fail(LLAMPC_E_ARG, "%s", why);
   return LLAMPC_OK;
 }
 
@@ -865,36 +883,33 @@ extern "C" int llampc_integrate_batch(const double* x0, const double* u, int64_t
   return LLAMPC_OK;
 }
 
-// The variant launch_plan picks for the given-xref layout, from the same functions it calls.
+// The variant a given-xref look-ahead of these sizes takes, without or with a corridor: the
+// launch's own plan_shape.
+static void plan_variant(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share, bool corridor,
+                         int32_t out[4]) {
+  const PlanShape s = lookahead_shape(n, true, C, H, integrator, LLAMPC_XREF_GIVEN, share, false, corridor);
+  out[0] = s.lpm;
+  out[1] = s.G;
+  out[2] = s.cpl;
+  out[3] = s.stage ? 1 : 0;
+}
+
 extern "C" int llampc_plan_variant(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share,
                                    int32_t out[4]) {
   if (!out) return fail(LLAMPC_E_ARG, "NULL argument");
   if (n < 1 || C < 1 || H < 1 || integrator < LLAMPC_RK4 || integrator > LLAMPC_RK6)
     return fail(LLAMPC_E_ARG, "n %lld, C %d, H %d, integrator %d", (long long)n, C, H, integrator);
-  const int G = lookahead_group(C);
-  bool stage = false;
-  (void)lookahead_lds_bytes(C, H, &stage);
-  out[0] = lookahead_lpm(n, C, integrator, share);
-  out[1] = G;
-  out[2] = (C + G - 1) / G;
-  out[3] = stage ? 1 : 0;
+  plan_variant(n, C, H, integrator, share, false, out);
   return LLAMPC_OK;
 }
 
-// The variant a corridor launch takes (launch_plan with a PlanCorridor): the same functions.
 extern "C" int llampc_plan_variant_corridor(int64_t n, int32_t C, int32_t H, int32_t integrator, int32_t share,
                                             int32_t out[4]) {
   if (!out) return fail(LLAMPC_E_ARG, "NULL argument");
   if (n < 1 || C < 1 || H < 1 || (integrator != LLAMPC_RK4 && integrator != LLAMPC_EULER_NLP))
     return fail(LLAMPC_E_ARG, "n %lld, C %d, H %d, integrator %d (the corridor look-ahead: RK4 or NLP-Euler)",
                 (long long)n, C, H, integrator);
-  const int G = lookahead_group(C);
-  bool stage = false;
-  (void)lookahead_lds_bytes_corridor(C, H, &stage);
-  out[0] = lookahead_lpm(n, C, integrator, share);
-  out[1] = G;
-  out[2] = (C + G - 1) / G;
-  out[3] = stage ? 1 : 0;
+  plan_variant(n, C, H, integrator, share, true, out);
   return LLAMPC_OK;
 }
 

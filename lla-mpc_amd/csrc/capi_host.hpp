@@ -1,6 +1,7 @@
 // capi_host.hpp — the C ABI's host arithmetic (capi*.hip): sequence numbers, poll bounds, the
-// input pack, the window unroll and the launch-argument fields that come from the bank.  Pure:
-// no HIP runtime call, so tests/native/capi_host.cpp runs all of it on a machine with no GPU.
+// input pack, the window unroll, the launch-argument fields that come from the bank and the
+// controller launch's shape (the plan launch's: launch_shape.hpp).  Pure: no HIP runtime call, so
+// tests/native/capi_host.cpp runs all of it on a machine with no GPU.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -9,7 +10,9 @@
 #include <cstring>
 
 #include "ctl.hpp"
+#include "ctl_lds.hpp"
 #include "kernels.hpp"
+#include "launch_shape.hpp"
 #include "nlp.hpp"
 
 namespace llampc {

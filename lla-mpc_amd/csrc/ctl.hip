@@ -26,7 +26,7 @@
 // the tagged-word waits and a slot's result words), ctl_cand_dev.hpp (the candidates),
 // cs_dev.hpp (ConstantSpeed), ctl_lookahead_dev.hpp (a look-ahead block), ctl_spec_dev.hpp (the
 // speculative look-ahead: spec blocks, last in the grid) and ctl_complete_dev.hpp (the sharded
-// exchange and the completion).  Here: the kernels, their launchers and the LDS size.
+// exchange and the completion).  Here: the kernels and their launchers.
 #include "ctl.hpp"
 #include "cs_dev.hpp"
 #include "ctl_complete_dev.hpp"
@@ -161,28 +161,6 @@ hipError_t launch_constant_speed(const CsLaunch& a, hipStream_t s) {
   allow_lds(cs_kernel);
   hipLaunchKernelGGL(cs_kernel, dim3(1), dim3(kBlock), L.end, s, a);
   return hipGetLastError();
-}
-
-size_t ctl_lds_bytes(int H, int C, int n, int nb_lb, int K, size_t* poll_off, bool s4, int px_G, int n_spec) {
-  const CtlLds L = ctl_lds(H, C, n, s4);
-  const size_t M = (size_t)nb_lb * K, Lb = nb_lb;    // lb_final's region (launch_plan's formula)
-  const size_t lbf = kScratchBytes + 8 * (3 * M + Lb) + sizeof(Ent) * Lb * kWaves + 4 * (3 * M + Lb + LLAMPC_KMAX + 2) + 8 + 16;
-  const size_t rank = kScratchBytes + (size_t)kWaves * kRankBytes + kBlockMergeBytes;
-  const size_t px = px_G ? kScratchBytes + ctl_px_bytes(px_G, K) : 0;   // ctl_exchange's region
-  // the speculative look-ahead: a spec block's layout, the look-back blocks' ranking and the
-  // spec merge's two list buffers
-  // (sharded: then the ranks' lists, ctl_spec_exchange)
-  const size_t spec_px = px_G ? align16(2 * sizeof(Ent) * Lb * n_spec) + align16(16 * (size_t)px_G * n_spec) +
-                                    2 * sizeof(Ent) * (size_t)px_G * n_spec
-                              : 0;
-  const size_t spec = n_spec ? std::max(spec_lds(H, C).end,
-                                        kScratchBytes + std::max<size_t>(std::max<size_t>(12 * kBlock, 2 * sizeof(Ent) * Lb * n_spec),
-                                                                         spec_px))
-                             : 0;
-  size_t off = std::max(std::max(std::max(L.end, px), std::max(lbf, rank)), spec);
-  off = align16(off);
-  *poll_off = off;
-  return off + kCtlPollBytes;
 }
 
 template <bool PX>

@@ -408,10 +408,6 @@ struct CsLaunch {
 };
 hipError_t launch_constant_speed(const CsLaunch& a, hipStream_t s);
 
-// LDS bytes of the controller launch and the completing block's area offset (ctl.hip); s4:
-// with the staged input terms (CtlLaunch.s4).
-size_t ctl_lds_bytes(int H, int C, int n, int nb_lb, int K, size_t* poll_off, bool s4 = false, int px_G = 0,
-                     int n_spec = 0);
 hipError_t launch_ctl(const CtlLaunch& c, int lpm, size_t lds, hipStream_t s);
 
 }  // namespace llampc

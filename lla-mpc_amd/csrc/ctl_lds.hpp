@@ -1,10 +1,14 @@
 // ctl_lds.hpp — the controller launch's dynamic-LDS layouts, for the device and for the host's
-// size computation (ctl.hip ctl_lds_bytes): a look-ahead block's (CtlLds; cs_kernel's with C = 0),
+// size computation (ctl_lds_bytes): a look-ahead block's (CtlLds; cs_kernel's with C = 0),
 // a spec block's (SpecLds) and the size of the completing block's area, whose record words are
-// checked against the C structs here.  Included by the ctl_*_dev.hpp headers and ctl.hip.
+// checked against the C structs here.  No device code: included by the ctl_*_dev.hpp headers,
+// ctl.hip and capi_host.hpp (ctl_shape).
 #pragma once
+#include <algorithm>
+#include <cstddef>
+
 #include "ctl.hpp"
-#include "dev_wave.hpp"
+#include "launch_shape.hpp"
 
 namespace llampc {
 
@@ -60,6 +64,30 @@ __host__ __device__ __forceinline__ SpecLds spec_lds(int H, int C) {
   return L;
 }
 constexpr size_t kCtlPollBytes = 4096;   // ctl_complete's area (layout there)
+
+// LDS bytes of the controller launch and the completing block's area offset; s4: with the staged
+// input terms (CtlLaunch.s4).
+inline size_t ctl_lds_bytes(int H, int C, int n, int nb_lb, int K, size_t* poll_off, bool s4 = false, int px_G = 0,
+                            int n_spec = 0) {
+  const CtlLds L = ctl_lds(H, C, n, s4);
+  const size_t Lb = nb_lb;
+  const size_t lbf = lb_final_lds_bytes(nb_lb, K);                      // lb_final's region, the wave lists
+  const size_t px = px_G ? kScratchBytes + ctl_px_bytes(px_G, K) : 0;   // ctl_exchange's region
+  // the speculative look-ahead: a spec block's layout, the look-back blocks' ranking and the
+  // spec merge's two list buffers
+  // (sharded: then the ranks' lists, ctl_spec_exchange)
+  const size_t spec_px = px_G ? align16(2 * sizeof(Ent) * Lb * n_spec) + align16(16 * (size_t)px_G * n_spec) +
+                                    2 * sizeof(Ent) * (size_t)px_G * n_spec
+                              : 0;
+  const size_t spec = n_spec ? std::max(spec_lds(H, C).end,
+                                        kScratchBytes + std::max<size_t>(std::max<size_t>(12 * kBlock, 2 * sizeof(Ent) * Lb * n_spec),
+                                                                         spec_px))
+                             : 0;
+  size_t off = std::max(std::max(std::max(L.end, px), lbf), spec);
+  off = align16(off);
+  *poll_off = off;
+  return off + kCtlPollBytes;
+}
 // ctl_complete's record words (one 8-byte word per lane of wave 0)
 static_assert(offsetof(llampc_plan_out, window_full) == 4 && offsetof(llampc_plan_out, K) == 8 &&
                   offsetof(llampc_plan_out, sel_owned) == 12 && offsetof(llampc_plan_out, lb_best) == 16 &&

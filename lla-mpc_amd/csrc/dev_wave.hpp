@@ -7,7 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels.hpp"
+#include "launch_shape.hpp"
 
 namespace llampc {
 
@@ -251,14 +251,10 @@ __device__ __forceinline__ const T& kernarg_at(KernargPtr p, int off) {
 // G17): [0,64) sv[2][4] double | [64,128) si[2][4] int64 | [128,160) sn[8] int32 (the
 // 8-wave work-queue block's la_publish uses all 8) | [160,164) the ticket flag (kFlagOff) |
 // [168,176) the poller's per-wave late flags (kLateOff) | pad to 192 | role-specific region
-// from 192.
-constexpr int kScratchBytes = 192;
+// from 192 (kScratchBytes, with the other sizes the launch's LDS request is made of:
+// launch_shape.hpp).
 constexpr int kFlagOff = 160;
 constexpr int kLateOff = 168;
-constexpr int kStageW = 8;              // doubles per staged (step, candidate) input
-constexpr int kRankBytes = 64 * 8 + 64 * 4 + 256;   // wave_topk_rank: keys + ids per wave (+pad)
-constexpr int kWaves = kBlock / 64;     // look-back lists per block (one per wave)
-constexpr int kListsPerLane = 8;        // lb_final: lists per lane of the merging wave
 
 struct Scratch {
   double* sv;

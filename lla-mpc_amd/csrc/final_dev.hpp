@@ -9,11 +9,6 @@
 
 namespace llampc {
 
-struct Ent {
-  double v;
-  int64_t i;
-};
-
 __device__ __forceinline__ bool ent_less(const Ent& x, const Ent& y) {
   return less_nan_last(x.v, x.i, y.v, y.i);
 }

@@ -20,9 +20,7 @@
 // The plan kernels are in plan_dev.hpp (their device code in the *_dev.hpp role headers), their
 // instantiations in plan_*.hip
 // (one TU per variant group, so the library builds in parallel), the controller tick in ctl.hip.
-#include <stdlib.h>
-
-#include <algorithm>
+#include <type_traits>
 
 #include "dev_wave.hpp"
 #include "final_dev.hpp"
@@ -265,97 +263,6 @@ __global__ __launch_bounds__(kBlock) void integrate_kernel(const double* x0, con
 // ------------------------------------------------------------------------------------
 // Launchers
 // ------------------------------------------------------------------------------------
-int lookback_blocks(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-
-// Lanes (candidate slots) per model: the power of two >= C, at most one block (256); a
-// model's candidates beyond G run sequentially in its lanes (cpl = ceil(C / G)).
-int lookahead_group(int32_t C) {
-  int G = 1;
-  while (G < C && G < kBlock) G <<= 1;
-  return G;
-}
-
-// Lanes per rollout while the launch has fewer waves than the chip has SIMDs (latency-
-// bound: a wave's time is its instruction stream): a quad (LPM = 4: front chain, rear
-// chain, sin psi, cos psi in one stream) up to 16k rollouts, a lane pair (front / rear
-// chain) up to 32k; one lane per rollout once the chip fills (fewest instructions per
-// rollout).
-// share: the number of banks the caller ticks concurrently on the device (llampc_bank_set_
-// concurrency): each launch is sized for 1/share of the SIMDs (BASELINE config 5, two tracks
-// at N = 10^4, H = 40: LPM 2 instead of 4, so both launches are resident together — 111 ->
-// 86 us per paced step, profiles/r04/config5_lpm.log).
-int lookahead_lpm(int64_t n, int32_t C, int32_t integrator, int32_t share) {
-  if (integrator == LLAMPC_RK6) return 1;
-  const int G = lookahead_group(C);
-  if (const char* e = getenv("LLAMPC_LPM")) {     // benchmarking override
-    const int v = atoi(e);
-    if (v == 1 || ((v == 2 || v == 4) && v * G <= kBlock)) return v;
-  }
-  const int64_t lanes = n * G * std::max(share, 1);
-  if (lanes <= 16384 && 4 * G <= kBlock) return 4;
-  return (lanes <= 32768 && 2 * G <= kBlock) ? 2 : 1;
-}
-
-int lookahead_blocks(int64_t n, int32_t C, int lpm) {
-  const int mpb = kBlock / (lookahead_group(C) * lpm);
-  return (int)((n + mpb - 1) / mpb);
-}
-
-// Staged inputs per (step, candidate): RK4 the fused stages' input terms and delta, else pwm,
-// delta, sin delta, cos delta; then the input-rate cost term and the feasibility (1/0) —
-// kStageW doubles.  One block per CU (the launch's LDS
-// request), so the staging may use most of the CU's 160 KiB.
-constexpr size_t kStageLimit = 128 * 1024;
-
-// knots [n] + the +inf pad [kKnotPad] + xy [8(n-1)] + mus [M] (padded to 16 B) (the speed
-// window on top: launch_plan)
-size_t raceline_lds_bytes(int32_t n, int32_t M) {
-  return 8 * (size_t)(n + kKnotPad) + 64 * (size_t)(n - 1) + 8 * (size_t)((M + 1) & ~1);
-}
-
-size_t lookahead_lds_bytes(int32_t C, int32_t H, bool* stage_u) {
-  const size_t base = kScratchBytes + 16 * (size_t)(H + 1);
-  const size_t ub = 8 * kStageW * (size_t)C * H;
-  *stage_u = base + ub <= kStageLimit;
-  return *stage_u ? base + ub : base;
-}
-
-// The corridor launch: hp [H][6] (48 H bytes) behind the staged inputs; a shape whose inputs no
-// longer fit beside it goes unstaged.
-size_t lookahead_lds_bytes_corridor(int32_t C, int32_t H, bool* stage_u) {
-  const size_t base = kScratchBytes + 16 * (size_t)(H + 1) + 48 * (size_t)H;
-  const size_t ub = 8 * kStageW * (size_t)C * H;
-  *stage_u = base + ub <= kStageLimit;
-  return *stage_u ? base + ub : base;
-}
-
-// Models per look-back lane: keep the block lists small enough for the in-LDS tree merge
-// (nb_lb * K <= 640 entries = 20 KB for both buffers).
-// Models per lane: lb_final holds blocks * kWaves * K entries in LDS and merges at most
-// 64 * kListsPerLane lists; R grows once blocks * K would pass 640 (40 KB of LDS) or the
-// blocks 64 * kListsPerLane / kWaves.
-int lookback_r(int64_t n, int32_t K) {
-  const int64_t blocks = std::min<int64_t>(640 / std::max(1, K), 64 * kListsPerLane / kWaves);
-  const int64_t per = (int64_t)kBlock * std::max<int64_t>(1, blocks);   // models per R step
-  return (int)std::max<int64_t>(1, (n + per - 1) / per);
-}
-
-int lookback_blocks_r(int64_t n, int R) { return (int)((n + (int64_t)kBlock * R - 1) / ((int64_t)kBlock * R)); }
-
-// Every plan launch requests more than half of the CU's 160 KiB of LDS, so each block has
-// its CU — and each wave its SIMD — to itself.  (Letting LPM-1 launches pack two blocks per
-// CU measured no gain at C = 64: 567-574 vs 568-569 us.)  Every cross-block hand-off is an
-// agent-scope atomic (sc1: L1-bypassing, st_wt / ld_wt).
-
-bool plan_inline_ok(int32_t C, int32_t H, int32_t integrator, int32_t xref_mode) {
-  if (integrator != LLAMPC_RK4 || xref_mode != LLAMPC_XREF_GIVEN || C < 1 || H < 1) return false;
-  if (16 + 2 * ((int64_t)H + 1) + 2 * (int64_t)C * H > kInlineDoubles) return false;
-  bool stage = false;
-  (void)lookahead_lds_bytes(C, H, &stage);
-  return stage;
-}
-
-
 // Compute units of the current device (cached): the work-queue layout launches one
 // look-ahead block per CU, minus the one the completing look-back block holds.
 static int device_cus() {
@@ -370,126 +277,74 @@ static int device_cus() {
   return cus[d];
 }
 
+// f(I, L) with the runtime (integrator, lanes per rollout) of an RK4 or NLP-Euler launch as
+// std::integral_constants: the instantiated variant groups of kernels.hpp, {0, 1} x {4, 2, 1}.
+template <class F>
+static void with_variant(int integ, int lpm, F&& f) {
+  const auto with_lpm = [&](auto I) {
+    if (lpm == 4) f(I, std::integral_constant<int, 4>{});
+    else if (lpm == 2) f(I, std::integral_constant<int, 2>{});
+    else f(I, std::integral_constant<int, 1>{});
+  };
+  if (integ == LLAMPC_RK4) with_lpm(std::integral_constant<int, 0>{});
+  else with_lpm(std::integral_constant<int, 1>{});
+}
+
 hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, FinalLaunch f,
                        hipStream_t s, const InlinePack* pk, int32_t share, const PlanCorridor* cor) {
-  // the corridor launch: RK4 or NLP-Euler on the shared xref, device inputs, no peer exchange
-  if (cor && (!la || !cor->hp || pk || f.px_G || la->xref_mode != LLAMPC_XREF_GIVEN ||
-              (la->integrator != LLAMPC_RK4 && la->integrator != LLAMPC_EULER_NLP)))
-    return hipErrorInvalidValue;
+  if (cor && !cor->hp) return hipErrorInvalidValue;
+  // 1. the launch's shape (launch_shape.hpp): the one place that decides it, or refuses
+  PlanShapeIn in{};
+  in.n = lb ? lb->n : la ? la->n : 0;
+  in.lb = lb != nullptr;
+  if (lb) {
+    in.K = lb->K;
+    in.full = lb->full != 0;
+  }
+  in.la = la != nullptr;
+  if (la) {
+    in.C = la->C;
+    in.H = la->H;
+    in.integrator = la->integrator;
+    in.xref_mode = la->xref_mode;
+    in.rl_n = la->rl.n;
+    in.rl_M = la->rl.M;
+    in.wq_counter = la->wq != nullptr;
+  }
+  in.share = share;
+  in.px_G = f.px_G;
+  in.pack = pk != nullptr;
+  in.corridor = cor != nullptr;
+  const PlanShape sh = plan_shape(in, device_cus());
+  if (sh.refuse) return hipErrorInvalidValue;
+  // 2. what the kernels read of it
   LookbackLaunch lbv{};
   LookaheadLaunch lav{};
-  int G = 1, cpl = 1, lpm = 1, integ = LLAMPC_RK4;
-  bool stage = false;
-  size_t lds = kScratchBytes;
-  f.nb_lb = 0;
-  f.nb_la = 0;
   if (lb) {
     lbv = *lb;
-    lbv.R = lookback_r(lb->n, std::max(1, lb->K));
-    // A/B knob: at least LLAMPC_LB_R models per look-back lane (fewer look-back blocks)
-    static const int r_min = getenv("LLAMPC_LB_R") ? std::max(1, atoi(getenv("LLAMPC_LB_R"))) : 1;
-    lbv.R = std::max(lbv.R, r_min);
-    f.nb_lb = lookback_blocks_r(lb->n, lbv.R);
-    if (lb->full) {
-      const size_t M = (size_t)f.nb_lb * lb->K, L = f.nb_lb;   // lb_final (layout there)
-      lds = std::max(lds, kScratchBytes + 8 * (3 * M + L) + sizeof(Ent) * L * kWaves +
-                              4 * (3 * M + L + LLAMPC_KMAX + 2) + 8 + 16);
-      lds = std::max(lds, kScratchBytes + (size_t)kWaves * kRankBytes + kBlockMergeBytes);  // wave lists
-    }
+    lbv.R = sh.R;
   }
   if (la) {
     lav = *la;
-    G = lookahead_group(la->C);
-    cpl = (la->C + G - 1) / G;
-    integ = la->integrator;
-    lpm = lookahead_lpm(la->n, la->C, integ, share);
-    f.nb_la = lookahead_blocks(la->n, la->C, lpm);
-    if (la->xref_mode == LLAMPC_XREF_RACELINE) {
-      // knots + x/y rows in LDS, the staged inputs when they fit beside them, and the rest
-      // of the CU's LDS (up to the whole track) for the speed-profile window
-      constexpr size_t kLdsMax = 160 * 1024 - 1024;
-      const size_t rl = raceline_lds_bytes(la->rl.n, la->rl.M);
-      size_t base = lookahead_lds_bytes(la->C, la->H, &stage);
-      if (base + rl > kLdsMax) {
-        stage = false;
-        base = kScratchBytes + 16 * (size_t)(la->H + 1);
-      }
-      const size_t per_seg = 32 * (size_t)std::max(1, la->rl.M);
-      const size_t room = base + rl < kLdsMax ? kLdsMax - base - rl : 0;
-      lav.rl.wcap = (int32_t)std::min<size_t>(room / per_seg, (size_t)(la->rl.n - 1));
-      lds = std::max(lds, base + rl + per_seg * (size_t)lav.rl.wcap);
-    } else if (cor) {
-      lds = std::max(lds, lookahead_lds_bytes_corridor(la->C, la->H, &stage));
-    } else {
-      lds = std::max(lds, lookahead_lds_bytes(la->C, la->H, &stage));
-    }
+    lav.rl.wcap = sh.wcap;
   }
+  f.nb_lb = sh.nb_lb;
+  f.nb_la = sh.nb_la;
   f.do_lb = lb != nullptr;
   f.do_la = la != nullptr;
-  if (f.nb_lb + f.nb_la == 0) return hipErrorInvalidValue;
-  // Work queue (the throughput regime): LPM 1 with a model inside one wave (G <= 64), RK4 on
-  // the shared xref, device inputs, at least 1.75 rounds of look-ahead blocks per CU — then one
-  // block per CU (minus the completing look-back block's) takes units of models from the
-  // bank's counter: 8 waves per block (two rollout waves per SIMD) from 4 units per wave
-  // slot of the 4-wave layout on, else 4 waves.  C = 64 N-sweep on one box (static / 4-wave /
-  // 8-wave, us per tick; profiles/r03/v31/c64_sweep.txt): N = 1500: 92.0 / 99.5 / 106.9;
-  // 2000: 128.1 / 106.5 / 155.8; 3000: 163.9 / 137.7 / 164.4; 5000: 239.4 / 206.3 / 209.5;
-  // 10^4: 468.7 / 391.2 / 372.6; 2 10^4: 899.7 / 732.2 / 681.4 — the 8-wave layout's second
-  // wave of a SIMD only fills the first one's bubbles, so with few units per wave the launch
-  // waits for those slow units.  LLAMPC_NO_WQ=1 keeps the block-per-models layout,
-  // LLAMPC_WQ_WAVES=4|8 forces a work-queue block size (A/B runs).
-  int wq = 0;
-  if (la && la->wq && lpm == 1 && G <= 64 && integ == LLAMPC_RK4 && la->xref_mode == LLAMPC_XREF_GIVEN &&
-      !pk && !cor && getenv("LLAMPC_NO_WQ") == nullptr) {
-    const int nw = std::max(1, device_cus() - 1);
-    const char* force = getenv("LLAMPC_WQ_WAVES");
-    const int forced = force ? atoi(force) : 0;
-    if ((int64_t)f.nb_la * 4 >= (int64_t)nw * 7 || (forced && f.nb_la > nw)) {
-      const int64_t mpw = 64 / G;
-      const int64_t units = (la->n + mpw - 1) / mpw;
-      f.nb_la = nw;
-      wq = (stage && (forced ? forced == 8 : units >= 4 * (int64_t)nw * kWaves)) ? 2 : 1;
-    }
-  }
-  if (f.px_G) {                          // fused peer exchange: RK4, given xref, device inputs
-    if (pk || integ != LLAMPC_RK4 || (la && la->xref_mode == LLAMPC_XREF_RACELINE) || f.px_G > kPeerFuseMax)
-      return hipErrorInvalidValue;
-    lds = std::max(lds, 256 + (size_t)f.px_G * (sizeof(llampc_plan_out) + 2 * LLAMPC_KMAX * sizeof(EntS)) +
-                            kWaves * sizeof(int));
-  }
-
-  if (pk) {
-    if (!la || !plan_inline_ok(la->C, la->H, integ, la->xref_mode) || !stage) return hipErrorInvalidValue;
-    if (lpm == 4) launch_plan_inline_group<4>(lbv, lav, f, G, cpl, lds, s, *pk);
-    else if (lpm == 2) launch_plan_inline_group<2>(lbv, lav, f, G, cpl, lds, s, *pk);
-    else launch_plan_inline_group<1>(lbv, lav, f, G, cpl, lds, s, *pk);
-    return hipGetLastError();
-  }
-  if (cor) {                             // block per models, the unsplit rollouts (plan_kernel_corr)
-    const bool rk4 = integ == LLAMPC_RK4;
-    if (lpm == 4) (rk4 ? launch_plan_corridor_group<0, 4> : launch_plan_corridor_group<1, 4>)(lbv, lav, f, G, cpl, stage, lds, s, *cor);
-    else if (lpm == 2) (rk4 ? launch_plan_corridor_group<0, 2> : launch_plan_corridor_group<1, 2>)(lbv, lav, f, G, cpl, stage, lds, s, *cor);
-    else (rk4 ? launch_plan_corridor_group<0, 1> : launch_plan_corridor_group<1, 1>)(lbv, lav, f, G, cpl, stage, lds, s, *cor);
-    return hipGetLastError();
-  }
-  switch (integ) {
-    case LLAMPC_RK4:
-    case LLAMPC_EULER_NLP: {
-      const bool rk4 = integ == LLAMPC_RK4;
-      const int w = rk4 ? wq : 0;
-      if (lpm == 4) (rk4 ? launch_plan_group<0, 4> : launch_plan_group<1, 4>)(lbv, lav, f, G, cpl, stage, lds, s, w);
-      else if (lpm == 2) (rk4 ? launch_plan_group<0, 2> : launch_plan_group<1, 2>)(lbv, lav, f, G, cpl, stage, lds, s, w);
-      else (rk4 ? launch_plan_group<0, 1> : launch_plan_group<1, 1>)(lbv, lav, f, G, cpl, stage, lds, s, w);
-      break;
-    }
-    case LLAMPC_RK6:
-      launch_plan_group<2, 1>(lbv, lav, f, G, cpl, stage, lds, s, 0);
-      break;
-    default: return hipErrorInvalidValue;
+  // 3. the variant group's launcher
+  if (sh.integ == LLAMPC_RK6) {
+    launch_plan_group<2, 1>(lbv, lav, f, sh.G, sh.cpl, sh.stage, sh.lds, s, 0);
+  } else {
+    with_variant(sh.integ, sh.lpm, [&](auto I, auto L) {
+      constexpr int kI = decltype(I)::value, kL = decltype(L)::value;
+      if (pk) launch_plan_inline_group<kL>(lbv, lav, f, sh.G, sh.cpl, sh.lds, s, *pk);
+      else if (cor) launch_plan_corridor_group<kI, kL>(lbv, lav, f, sh.G, sh.cpl, sh.stage, sh.lds, s, *cor);
+      else launch_plan_group<kI, kL>(lbv, lav, f, sh.G, sh.cpl, sh.stage, sh.lds, s, sh.wq);
+    });
   }
   return hipGetLastError();
 }
-
 
 hipError_t launch_merge(const llampc_plan_out* parts, int32_t G, int32_t nan_first,
                         llampc_plan_out* merged, hipStream_t s) {

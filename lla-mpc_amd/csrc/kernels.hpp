@@ -19,7 +19,7 @@ constexpr int kBlock = 256;            // 4 waves of 64 lanes
 constexpr int kBlockWQ = 512;
 // Work-queue layouts (plan kernel template argument WQ): 0 = none (block per models), 1 = one
 // 4-wave block per CU, 2 = one 8-wave block per CU (two rollout waves per SIMD; staged launches
-// only — the unstaged rollout would spill at 256 VGPRs).  launch_plan picks by the size of the
+// only — the unstaged rollout would spill at 256 VGPRs).  plan_shape picks by the size of the
 // queue (C = 64 N-sweep, profiles/r03/v31/c64_sweep.txt).
 constexpr int wq_threads(int wq) { return wq == 2 ? kBlockWQ : kBlock; }
 
@@ -67,7 +67,7 @@ struct LookaheadLaunch {
   uint64_t* blk_tag;                     // [blocks][5]: partial value hi, lo, key hi, lo, nf
   uint32_t seq;                          // this launch's tag (never 0)
   int32_t poll;
-  // work queue (launch_plan decides: LPM 1, G <= 64, more look-ahead blocks than CUs): the
+  // work queue (plan_shape decides: LPM 1, G <= 64, more look-ahead blocks than CUs): the
   // bank's unit counter, 0 at every launch's start (the block completing the record resets it
   // after every take of the launch, final_write)
   uint64_t* wq;
@@ -131,31 +131,22 @@ struct PlanCorridor {
   double weight;
 };
 
-int lookback_blocks(int64_t n);
-int lookahead_group(int32_t C);
-int lookahead_lpm(int64_t n, int32_t C, int32_t integrator, int32_t share = 1);
-int lookahead_blocks(int64_t n, int32_t C, int lpm);
-int lookback_r(int64_t n, int32_t K);               // models per look-back lane
-int lookback_blocks_r(int64_t n, int R);
-size_t lookahead_lds_bytes(int32_t C, int32_t H, bool* stage_u);
-// ... of a corridor launch: hp [H][6] behind the staged inputs, which stay staged only if both fit
-size_t lookahead_lds_bytes_corridor(int32_t C, int32_t H, bool* stage_u);
-size_t raceline_lds_bytes(int32_t n, int32_t M);
-
 // The whole tick in ONE launch: look-back blocks (if lb), look-ahead blocks (if la), and
-// the completion stages run by ticket winners; writes f.out.  f.nb_* / f.do_* are set here.
+// the completion stages run by ticket winners; writes f.out.  f.nb_* / f.do_*, the look-back's R
+// and the raceline's wcap are set here, from the launch's shape (launch_shape.hpp plan_shape: the
+// variant, the block counts, the LDS request), and what plan_shape refuses is
+// hipErrorInvalidValue with nothing enqueued.
 // pk != null: the inputs are in *pk (see InlinePack); needs a look-ahead with RK4, the
-// given xref and U staged in LDS (plan_inline_ok), else hipErrorInvalidValue.
+// given xref and U staged in LDS.
 // cor != null: the corridor launch (plan_kernel_corr) — block per models on the unsplit rollouts,
-// never the work queue, the inline pack or the fused peer exchange; hipErrorInvalidValue, with
-// nothing enqueued, for RK6, the raceline reference, pk or a peer exchange (f.px_G).
+// never the work queue, the inline pack or the fused peer exchange; refused for RK6, the raceline
+// reference, pk or a peer exchange (f.px_G).
 hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, FinalLaunch f,
                        hipStream_t s, const InlinePack* pk = nullptr, int32_t share = 1,
                        const PlanCorridor* cor = nullptr);
-bool plan_inline_ok(int32_t C, int32_t H, int32_t integrator, int32_t xref_mode);
 // The plan-kernel variant groups (plan_dev.hpp; one translation unit per group, plan_*.hip):
 // (integrator, lanes per rollout) with the staged / unstaged inputs and, for RK4 at LPM 1, the
-// work-queue layouts; the inline-pack host ticks per LPM.
+// work-queue layouts; the inline-pack host ticks per LPM.  lds: plan_shape's, every floor applied.
 template <int INTEG, int LPM>
 void launch_plan_group(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f, int G,
                        int cpl, bool stage, size_t lds, hipStream_t s, int wq);
@@ -217,7 +208,7 @@ struct PeerLaunch {
   uint32_t seq;                          // tick number, never 0 (the mailbox starts zeroed)
 };
 hipError_t launch_peer_exchange(const PeerLaunch& a, hipStream_t s);
-// Largest world the plan launch can merge in its own LDS (records + lists, see launch_plan).
+// Largest world the plan launch can merge in its own LDS (records + lists, see plan_shape).
 constexpr int kPeerFuseMax = 16;
 // The track corridor along a path (track_corridor_kernel; corridor_dev.hpp): one block per step
 // k = 1..H writes row k - 1 of hp [H][6] and theta [H] (or null).  The path [2][H+1] travels in the

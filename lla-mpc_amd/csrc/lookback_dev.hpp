@@ -86,21 +86,13 @@ __device__ __forceinline__ uint64_t order_key(double w) {
   const uint64_t b = (uint64_t)__double_as_longlong(wc);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-// A top-K entry in LDS: its key, its local model index (ids from kNoModelId up mark lanes
-// without a model: unique per slot, above every real index since n <= INT32_MAX) and value.
+// A top-K entry in LDS (BEnt, launch_shape.hpp): ids from kNoModelId up mark lanes without a model.
 constexpr uint32_t kNoModelId = 0xFFFFFE00u;
-struct BEnt {
-  uint64_t key;
-  uint32_t id;
-  uint32_t pos;
-  double v;
-};
 // (key, id, pos) order: total, so every rank below is unique.
 __device__ __forceinline__ bool bless(const BEnt& a, const BEnt& b) {
   return (int)(a.key < b.key) |
          ((int)(a.key == b.key) & ((int)(a.id < b.id) | ((int)(a.id == b.id) & (int)(a.pos < b.pos))));
 }
-constexpr int kBlockMergeBytes = kWaves * LLAMPC_KMAX * (int)sizeof(BEnt);
 
 // The block's sorted top-K from its waves' lists (kWaves x K entries staged in LDS by
 // wave_topk_rank or the R > 1 rounds): the first kWaves*K threads rank their entry among

@@ -11,13 +11,7 @@ namespace llampc {
 // Cross-shard merge after the all-gather: one wave.  Scalars by lane-parallel reads and
 // shuffles; the shards' sorted top-K lists by the LDS tree merge.  merge.hpp holds the
 // same semantics as straight-line host code (llampc_merge); the tests check both agree.
-// A top-K entry of the cross-shard merge with its position in the gathered lists.
-struct EntS {
-  double v;
-  int64_t i;
-  int32_t src;
-  int32_t pad;
-};
+// An entry of those lists: EntS (launch_shape.hpp).
 
 // The merge proper over G records already staged in LDS at `rec` (their sorted top-K lists
 // are ranked in `lists`, 2 G KMAX EntS); thread 0 writes the scalars, threads < KMAX the

@@ -3,8 +3,6 @@
 // instantiations are spread over plan_*.hip (one TU per integrator / lanes-per-rollout group,
 // compiled in parallel); kernels.hip holds the dispatcher and the other kernels.
 #pragma once
-#include <algorithm>
-
 #include "final_dev.hpp"
 #include "lookahead_dev.hpp"
 #include "lookback_dev.hpp"
@@ -126,8 +124,7 @@ __global__ __launch_bounds__(kBlock) void plan_kernel_corr(LookbackLaunch, Looka
                                                   kernarg_at<int>(kp, kArgG + 4), cor.hp, cor.weight);
 }
 
-constexpr size_t kOneBlockPerCuLds = 82 * 1024;
-
+// The launchers: lds is plan_shape's request (launch_shape.hpp), the one-block-per-CU floor included.
 template <int INTEG, bool STAGE, int PX, int WQ>
 static void launch_plan_wq(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f,
                            int G, int cpl, size_t lds, hipStream_t s) {
@@ -139,9 +136,8 @@ static void launch_plan_wq(const LookbackLaunch& lb, const LookaheadLaunch& la, 
 template <int INTEG, bool STAGE, int LPM>
 static void launch_plan_t(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f,
                           int G, int cpl, size_t lds, hipStream_t s, int wq = 0) {
-  lds = std::max(lds, kOneBlockPerCuLds);
   if constexpr (INTEG == LLAMPC_RK4 && LPM == 1) {
-    if (wq) {                            // work queue: given xref only (launch_plan checks)
+    if (wq) {                            // work queue: given xref only (plan_shape checks)
       if constexpr (STAGE) {
         if (wq == 2) {
           if (f.px_G) launch_plan_wq<INTEG, STAGE, 1, 2>(lb, la, f, G, cpl, lds, s);
@@ -155,7 +151,7 @@ static void launch_plan_t(const LookbackLaunch& lb, const LookaheadLaunch& la, c
     }
   }
   if constexpr (INTEG == LLAMPC_RK4) {
-    if (f.px_G) {                        // given xref only (launch_plan checks)
+    if (f.px_G) {                        // given xref only (plan_shape checks)
       allow_lds(plan_kernel<INTEG, STAGE, LPM, 0, true>);
       hipLaunchKernelGGL((plan_kernel<INTEG, STAGE, LPM, 0, true>), dim3(f.nb_lb + f.nb_la), dim3(kBlock), lds,
                          s, lb, la, f, G, cpl);
@@ -176,7 +172,6 @@ static void launch_plan_t(const LookbackLaunch& lb, const LookaheadLaunch& la, c
 template <int LPM>
 static void launch_plan_inl(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f,
                             int G, int cpl, size_t lds, hipStream_t s, const InlinePack& pk) {
-  lds = std::max(lds, kOneBlockPerCuLds);
   allow_lds(plan_kernel_inl<LPM>);
   hipLaunchKernelGGL((plan_kernel_inl<LPM>), dim3(f.nb_lb + f.nb_la), dim3(kBlock), lds, s, lb, la, f,
                      G, cpl, pk);
@@ -200,7 +195,6 @@ void launch_plan_inline_group(const LookbackLaunch& lb, const LookaheadLaunch& l
 template <int INTEG, bool STAGE, int LPM>
 static void launch_plan_corr(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f, int G,
                              int cpl, size_t lds, hipStream_t s, const PlanCorridor& cor) {
-  lds = std::max(lds, kOneBlockPerCuLds);
   allow_lds(plan_kernel_corr<INTEG, STAGE, LPM>);
   hipLaunchKernelGGL((plan_kernel_corr<INTEG, STAGE, LPM>), dim3(f.nb_lb + f.nb_la), dim3(kBlock), lds, s, lb, la, f,
                      G, cpl, cor);

@@ -124,7 +124,45 @@ int main(int argc, char** argv) {
     const BankView b = fake_bank();
     print_builders("plan", b, (int32_t)arg(2));
     print_builders("ctl", b, LLAMPC_RK4);
-  } else if (mode == "spin") {           // spin code: a tag that never comes, 1 ms bound, on_timeout returns code
+  } else if (mode == "shape") {          // shape cus field=value ...: plan_shape of the named PlanShapeIn fields
+    PlanShapeIn in{};
+    in.share = 1;
+    for (int i = 3; i < argc; ++i) {
+      const std::string a = argv[i];
+      const size_t eq = a.find('=');
+      if (eq == std::string::npos) return 2;
+      const std::string k = a.substr(0, eq);
+      const long long v = std::strtoll(a.c_str() + eq + 1, nullptr, 0);
+      if (k == "n") in.n = v;
+      else if (k == "K") in.K = (int32_t)v;
+      else if (k == "lb") in.lb = v != 0;
+      else if (k == "full") in.full = v != 0;
+      else if (k == "la") in.la = v != 0;
+      else if (k == "C") in.C = (int32_t)v;
+      else if (k == "H") in.H = (int32_t)v;
+      else if (k == "integrator") in.integrator = (int32_t)v;
+      else if (k == "xref_mode") in.xref_mode = (int32_t)v;
+      else if (k == "rl_n") in.rl_n = (int32_t)v;
+      else if (k == "rl_M") in.rl_M = (int32_t)v;
+      else if (k == "share") in.share = (int32_t)v;
+      else if (k == "px_G") in.px_G = (int32_t)v;
+      else if (k == "pack") in.pack = v != 0;
+      else if (k == "corridor") in.corridor = v != 0;
+      else if (k == "wq_counter") in.wq_counter = v != 0;
+      else return 2;
+    }
+    const PlanShape s = plan_shape(in, (int)arg(2));
+    std::printf("family %d\ninteg %d\nlpm %d\nG %d\ncpl %d\nstage %d\nwq %d\npx %d\nxm %d\nR %d\nnb_lb %d\nnb_la %d\n"
+                "threads %d\nlds %zu\nwcap %d\nrefuse %s\n",
+                (int)s.family, s.integ, s.lpm, s.G, s.cpl, (int)s.stage, s.wq, (int)s.px, (int)s.xm, s.R, s.nb_lb,
+                s.nb_la, s.threads, s.lds, s.wcap, s.refuse ? s.refuse : "-");
+  } else if (mode == "ctl_shape") {      // ctl_shape n C H K rl_n warm do_lb no_stage px_G
+    const CtlShape s = ctl_shape(arg(2), (int32_t)arg(3), (int32_t)arg(4), (int32_t)arg(5), (int32_t)arg(6),
+                                 arg(7) != 0, arg(8) != 0, arg(9) != 0, (int)arg(10));
+    std::printf("lpm %d\nG %d\ncpl %d\nmpb %d\ns4 %d\nzfit %d\nR %d\nnb_lb %d\nnb_la %d\nnslots %d\nlds %zu\n"
+                "poll_off %zu\n",
+                s.lpm, s.G, s.cpl, s.mpb, s.s4, s.zfit, s.R, s.nb_lb, s.nb_la, s.nslots, s.lds, s.poll_off);
+  } else if (mode == "spin") {          // spin code: a tag that never comes, 1 ms bound, on_timeout returns code
     uint64_t tag = 41;
     int timeouts = 0;
     const auto never = [](uint64_t) { return false; };

@@ -1,7 +1,8 @@
 """csrc/capi_host.hpp (the C ABI's pure host helpers: tick numbers, poll bounds, the input
-pack, the window unroll, the raceline view and the launch fields that come from the bank)
-compiled for the host with AddressSanitizer and UBSan and run on the CPU.  The harness
-(tests/native/capi_host.cpp) prints values; what they must be is worked out here."""
+pack, the window unroll, the raceline view, the launch fields that come from the bank and the
+controller launch's shape) and csrc/launch_shape.hpp (the plan launch's shape) compiled for the
+host with AddressSanitizer and UBSan and run on the CPU.  The harness (tests/native/capi_host.cpp)
+prints values; what they must be is worked out here."""
 import os
 import shutil
 import subprocess
@@ -30,7 +31,7 @@ def harness(tmp_path_factory):
     subprocess.run(cmd, check=True, capture_output=True)
 
     def run(*args, env=None):
-        e = {k: v for k, v in os.environ.items() if not k.startswith("LLAMPC_POLL_")}
+        e = {k: v for k, v in os.environ.items() if not k.startswith("LLAMPC_")}   # every knob: the test's own
         e.update(ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1", **(env or {}))
         r = subprocess.run([out, *map(str, args)], capture_output=True, text=True, env=e)
         assert r.returncode == 0, r.stderr
@@ -171,3 +172,384 @@ def test_spin_for_tag(harness, code):
     assert (e_arg, e_hip) == (-1, -2) and stopped > 0 and timeout > 0 and stopped != timeout
     assert now == [0, stopped, 0]                    # arrived; stopped; on_timeout never ran
     assert late == [code, timeout, 0, 3]             # passed on; timed out; arrived during on_timeout
+
+
+# ---- the plan launch's shape (csrc/launch_shape.hpp plan_shape) and the controller's (ctl_shape) ----------
+# The rule, restated here from DESIGN.md ("The launch dispatch") and the header's comments; the harness's
+# `shape` mode prints every PlanShape field for the PlanShapeIn fields and the CU count it is given.
+KIB = 1024
+BLOCK, WAVES, KMAX = 256, 4, 32
+SCRATCH = 192                                   # the carve every block role starts with
+RANK_BYTES = 64 * 8 + 64 * 4 + 256              # a wave's ranking lists
+ENT, ENTS, BENT = 16, 24, 24                    # sizeof(Ent), sizeof(EntS), sizeof(BEnt)
+PLAN_OUT = 16 + 16 + 24 + 24 + KMAX * (8 + 8 + 8 + 8 + 4 + 8)   # sizeof(llampc_plan_out), test_host_cpu.py
+KNOT_PAD = 8
+STAGE_LIMIT, ONE_BLOCK_PER_CU, PLAN_LDS_MAX = 128 * KIB, 82 * KIB, 159 * KIB
+INLINE_DOUBLES, PEER_FUSE_MAX = 352, 16
+PLAIN, INLINE, CORRIDOR = 0, 1, 2
+SHAPE_DEFAULTS = dict(n=0, K=0, lb=0, full=0, la=0, C=0, H=0, integrator=RK4, xref_mode=XREF_GIVEN, rl_n=0, rl_M=0,
+                      share=1, px_G=0, pack=0, corridor=0, wq_counter=0)
+NO = dict(
+    corridor_la="the corridor belongs to the look-ahead: do_lookahead is 0",
+    corridor_rk6="the corridor look-ahead has no RK6 rollout",
+    corridor_raceline="the corridor look-ahead takes the given xref only (not LLAMPC_XREF_RACELINE)",
+    corridor_inputs="the corridor launch takes device inputs and no fused peer exchange",
+    integrator="unknown integrator",
+    work="nothing to launch: no look-back and no look-ahead block",
+    peer="the fused peer exchange: RK4, the given xref, device inputs, at most kPeerFuseMax ranks",
+    pack="the inline pack: an RK4 look-ahead on the given xref, staged, within kInlineDoubles")
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def group(C):
+    G = 1
+    while G < C and G < BLOCK:
+        G *= 2
+    return G
+
+
+def lpm_rule(n, C, integrator, share, env):
+    """4 lanes per rollout up to 16384 lanes (n G share), 2 up to 32768, else 1, each only while
+    lpm G <= 256; RK6 always 1; LLAMPC_LPM taken while v G <= 256."""
+    if integrator == RK6:
+        return 1
+    G = group(C)
+    v = int(env.get("LLAMPC_LPM", 0))
+    if v == 1 or (v in (2, 4) and v * G <= BLOCK):
+        return v
+    lanes = n * G * max(share, 1)
+    if lanes <= 16384 and 4 * G <= BLOCK:
+        return 4
+    return 2 if lanes <= 32768 and 2 * G <= BLOCK else 1
+
+
+def lookahead_lds(C, H, extra=0):
+    """scratch + xref [H+1][2] + extra, and the staged inputs (64 B per candidate and step) while all of
+    it stays within 128 KiB."""
+    base, ub = SCRATCH + 16 * (H + 1) + extra, 64 * C * H
+    return (base + ub, True) if base + ub <= STAGE_LIMIT else (base, False)
+
+
+def lookback_r(n, K):
+    return max(1, cdiv(n, BLOCK * max(1, min(640 // max(1, K), 64 * 8 // WAVES))))
+
+
+def lb_final_lds(nb_lb, K):
+    M, L = nb_lb * K, nb_lb
+    return max(SCRATCH + 8 * (3 * M + L) + ENT * L * WAVES + 4 * (3 * M + L + KMAX + 2) + 8 + 16,
+               SCRATCH + WAVES * RANK_BYTES + WAVES * KMAX * BENT)
+
+
+def raceline_lds(n, M):
+    return 8 * (n + KNOT_PAD) + 64 * (n - 1) + 8 * ((M + 1) & ~1)
+
+
+def shape_model(cus, env, **fields):
+    f = dict(SHAPE_DEFAULTS, **fields)
+    n, C, H, la, lb = f["n"], f["C"], f["H"], f["la"], f["lb"]
+    integ = f["integrator"] if la else RK4
+    raceline = bool(la) and f["xref_mode"] == XREF_RACELINE
+    given = f["xref_mode"] == XREF_GIVEN
+    if f["corridor"]:
+        for bad, why in ((not la, "corridor_la"), (f["integrator"] == RK6, "corridor_rk6"), (not given, "corridor_raceline"),
+                         (f["pack"] or f["px_G"], "corridor_inputs")):
+            if bad:
+                return dict(refuse=NO[why])
+    if f["px_G"] and (f["pack"] or integ != RK4 or raceline or f["px_G"] > PEER_FUSE_MAX):
+        return dict(refuse=NO["peer"])
+    if f["pack"] and (not la or integ != RK4 or not given or C < 1 or H < 1):
+        return dict(refuse=NO["pack"])
+    if integ not in (RK4, EULER_NLP, RK6):
+        return dict(refuse=NO["integrator"])
+    s = dict(family=CORRIDOR if f["corridor"] else INLINE if f["pack"] else PLAIN, integ=integ, lpm=1, G=1, cpl=1, stage=0,
+             wq=0, px=int(f["px_G"] != 0), xm=int(raceline), R=0, nb_lb=0, nb_la=0, threads=BLOCK, wcap=0, refuse="-")
+    lds = SCRATCH
+    if lb:
+        s["R"] = max(lookback_r(n, max(1, f["K"])), max(1, int(env.get("LLAMPC_LB_R", 1))))
+        s["nb_lb"] = cdiv(n, BLOCK * s["R"])
+        if f["full"]:
+            lds = max(lds, lb_final_lds(s["nb_lb"], f["K"]))
+    if la:
+        s["G"] = group(C)
+        s["cpl"] = cdiv(C, s["G"])
+        s["lpm"] = lpm_rule(n, C, integ, f["share"], env)
+        s["nb_la"] = cdiv(n, BLOCK // (s["G"] * s["lpm"]))
+        if raceline:
+            # the knots and rows, the staged inputs if they fit beside them, the rest for the speed window
+            rl, per_seg = raceline_lds(f["rl_n"], f["rl_M"]), 32 * max(1, f["rl_M"])
+            base, stage = lookahead_lds(C, H)
+            if base + rl > PLAN_LDS_MAX:
+                base, stage = SCRATCH + 16 * (H + 1), False
+            s["wcap"] = min(max(PLAN_LDS_MAX - base - rl, 0) // per_seg, f["rl_n"] - 1)
+            lds = max(lds, base + rl + per_seg * s["wcap"])
+        else:
+            b, stage = lookahead_lds(C, H, 48 * H if f["corridor"] else 0)
+            lds = max(lds, b)
+        s["stage"] = int(stage)
+    if s["nb_lb"] + s["nb_la"] == 0:
+        return dict(refuse=NO["work"])
+    if (la and f["wq_counter"] and s["lpm"] == 1 and s["G"] <= 64 and integ == RK4 and given and not f["pack"]
+            and not f["corridor"] and "LLAMPC_NO_WQ" not in env):
+        nw, forced = max(1, cus - 1), int(env.get("LLAMPC_WQ_WAVES", 0))
+        if 4 * s["nb_la"] >= 7 * nw or (forced and s["nb_la"] > nw):
+            units = cdiv(n, 64 // s["G"])
+            s["nb_la"] = nw
+            s["wq"] = 2 if s["stage"] and (forced == 8 if forced else units >= 4 * nw * WAVES) else 1
+            s["threads"] = 512 if s["wq"] == 2 else BLOCK
+    if f["px_G"]:
+        lds = max(lds, 256 + f["px_G"] * (PLAN_OUT + 2 * KMAX * ENTS) + WAVES * 4)
+    if f["pack"] and (not s["stage"] or 16 + 2 * (H + 1) + 2 * C * H > INLINE_DOUBLES):
+        return dict(refuse=NO["pack"])
+    s["lds"] = max(lds, ONE_BLOCK_PER_CU)
+    return s
+
+
+def parse_fields(text):
+    out = {}
+    for ln in text.strip().splitlines():
+        k, _, v = ln.partition(" ")
+        out[k] = v if k == "refuse" else int(v)
+    return out
+
+
+@pytest.fixture(scope="module")
+def shape(harness):
+    """shape(cus, env=None, **fields): the harness's PlanShape, checked against shape_model field by field."""
+    def run(cus, env=None, **fields):
+        got = parse_fields(harness("shape", cus, *(f"{k}={int(v)}" for k, v in fields.items()), env=env))
+        want = shape_model(cus, env or {}, **fields)
+        if want["refuse"] != "-":
+            assert got["refuse"] == want["refuse"], (fields, got)
+        else:
+            assert got == want, (cus, env, fields)
+        return got
+    return run
+
+
+@pytest.fixture(scope="module")
+def nat():
+    from llampc import _native
+    _native.load()
+    return _native
+
+
+def test_shape_lpm_and_groups(shape):
+    """test_plan_variant_dispatch's cases (test_host_cpu.py) on the whole struct: the LPM thresholds
+    with share, RK6, the width limit, G / cpl from C, the LLAMPC_LPM override."""
+    la = lambda n, C_, integ=RK4, share=1, env=None: shape(256, env, n=n, la=1, C=C_, H=12, integrator=integ, share=share)
+    for integ in (RK4, EULER_NLP):
+        assert [la(n, 1, integ)["lpm"] for n in (16384, 16385, 32768, 32769)] == [4, 2, 2, 1]
+        assert [la(n, 64, integ)["lpm"] for n in (256, 257, 512, 513)] == [4, 2, 2, 1]
+        assert [la(n, 1, integ, 2)["lpm"] for n in (8192, 8193, 16384, 16385)] == [4, 2, 2, 1]
+        assert [la(n, 64, integ, 2)["lpm"] for n in (128, 129, 256, 257)] == [4, 2, 2, 1]
+    assert [la(n, C_, RK6)["lpm"] for n, C_ in ((1, 1), (97, 3), (97, 64), (10 ** 5, 1))] == [1, 1, 1, 1]
+    assert [la(3, C_)["lpm"] for C_ in (64, 65, 128, 129, 256, 1000)] == [4, 2, 2, 1, 1, 1]
+    for C_, G, cpl in ((1, 1, 1), (2, 2, 1), (3, 4, 1), (64, 64, 1), (65, 128, 1), (130, 256, 1), (257, 256, 2),
+                       (1000, 256, 4)):
+        v = la(97, C_)
+        assert (v["G"], v["cpl"], v["family"], v["integ"], v["threads"]) == (G, cpl, PLAIN, RK4, 256), (C_, v)
+        assert v["nb_la"] == cdiv(97, 256 // (G * v["lpm"])) and v["nb_lb"] == 0 and v["R"] == 0
+    for env, cases in (("4", ((10 ** 6, 64, 4), (97, 65, 2), (97, 130, 1))), ("2", ((10 ** 6, 128, 2), (97, 3, 2), (97, 130, 1))),
+                       ("1", ((97, 3, 1), (97, 130, 1))), ("3", ((97, 3, 4), (10 ** 6, 3, 1)))):
+        for n, C_, want in cases:
+            assert la(n, C_, env={"LLAMPC_LPM": env})["lpm"] == want, (env, n, C_)
+        assert la(97, 3, RK6, env={"LLAMPC_LPM": env})["lpm"] == 1
+
+
+WQ = dict(la=1, C=64, H=20, integrator=RK4, wq_counter=1, lb=1, K=10)
+
+
+def test_shape_work_queue_taken(shape):
+    """256 CUs, G = 64, LPM 1, RK4: one block per four models, so the queue opens at the first n with
+    4 ceil(n / 4) >= 255 x 7 = 1785 and runs 255 blocks; 8 waves from 4 x 255 x 4 = 4080 units (models,
+    at G = 64) on, when staged; the knobs."""
+    at = lambda n, env=None, **kw: shape(256, env, **dict(WQ, n=n, **kw))
+    assert 4 * cdiv(1784, 4) < 1785 <= 4 * cdiv(1785, 4)
+    a, b = at(1784), at(1785)
+    assert (a["wq"], a["nb_la"], a["lpm"]) == (0, 446, 1) and (b["wq"], b["nb_la"], b["threads"]) == (1, 255, 256)
+    a, b = at(4079), at(4080)
+    assert (a["wq"], a["nb_la"], a["threads"]) == (1, 255, 256) and (b["wq"], b["nb_la"], b["threads"]) == (2, 255, 512)
+    u = at(4080, H=32)                                           # C = 64, H = 32: unstaged, never 8 waves
+    assert (u["stage"], u["wq"], u["threads"]) == (0, 1, 256)
+    assert (at(5000, {"LLAMPC_NO_WQ": "1"})["wq"], at(5000, {"LLAMPC_NO_WQ": "1"})["nb_la"]) == (0, 1250)
+    assert at(1785, {"LLAMPC_WQ_WAVES": "8"})["wq"] == 2 and at(5000, {"LLAMPC_WQ_WAVES": "4"})["wq"] == 1
+    assert at(4080, {"LLAMPC_WQ_WAVES": "8"}, H=32)["wq"] == 1   # unstaged: 4 waves even when 8 are forced
+    # a forced block size opens the queue as soon as there are more blocks than CUs - 1
+    assert at(1100)["wq"] == 0 and (at(1100, {"LLAMPC_WQ_WAVES": "4"})["wq"], at(1100, {"LLAMPC_WQ_WAVES": "4"})["nb_la"]) == (1, 255)
+    assert at(1020, {"LLAMPC_WQ_WAVES": "4"})["wq"] == 0         # 255 blocks: not more than 255
+    # G = 8: 32 models per block, 8 per wave: open from 447 blocks (n = 14273), 8 waves from 4080 units (n = 32633)
+    g8 = lambda n: shape(256, None, **dict(WQ, n=n, C=8))
+    assert [g8(n)["wq"] for n in (14272, 14273, 32632, 32633)] == [0, 1, 1, 2]
+    # the CU count is an argument: 8 CUs, 7 blocks, open from 13 blocks, 8 waves from 112 units
+    s = shape(8, None, **dict(WQ, n=513))
+    assert (s["wq"], s["nb_la"], s["threads"]) == (2, 7, 512)
+    assert shape(104, None, **dict(WQ, n=1785))["nb_la"] == 103
+
+
+@pytest.mark.parametrize("why,kw", [
+    ("G > 64", dict(C=65)), ("NLP-Euler", dict(integrator=EULER_NLP)), ("RK6", dict(integrator=RK6)),
+    ("the raceline", dict(xref_mode=XREF_RACELINE, rl_n=700, rl_M=3)), ("an inline pack", dict(pack=1, H=2)),
+    ("a corridor", dict(corridor=1)), ("no counter", dict(wq_counter=0)), ("LPM 2 forced", dict(env={"LLAMPC_LPM": "2"}))])
+def test_shape_work_queue_never_taken(shape, why, kw):
+    kw = dict(kw)
+    env = kw.pop("env", None)
+    s = shape(256, env, **dict(WQ, n=5000, **kw))
+    assert s["wq"] == 0 and s["threads"] == 256 and s["nb_la"] == cdiv(5000, 256 // (s["G"] * s["lpm"])), (why, s)
+    assert shape(256, None, **dict(WQ, n=5000))["wq"] == 2      # the same launch without it
+
+
+@pytest.mark.parametrize("C_", [1, 3, 64, 130, 256])
+def test_shape_staging_boundary(shape, C_):
+    """Staged while 192 + 16 (H + 1) + 64 C H (+ 48 H with a corridor) <= 128 KiB: the last H that fits
+    and the next, without and with the corridor."""
+    for corridor, per_h in ((0, 16 + 64 * C_), (1, 16 + 48 + 64 * C_)):
+        H = (STAGE_LIMIT - SCRATCH - 16) // per_h
+        a, b = (shape(256, None, n=97, la=1, C=C_, H=h, corridor=corridor) for h in (H, H + 1))
+        assert (a["stage"], b["stage"]) == (1, 0), (C_, corridor, H)
+        assert a["lds"] == SCRATCH + 16 + per_h * H > ONE_BLOCK_PER_CU == b["lds"]
+        assert a["family"] == (CORRIDOR if corridor else PLAIN)
+
+
+def test_shape_staged_without_corridor_unstaged_with(shape):
+    a, b = (shape(256, None, n=97, la=1, C=31, H=64, corridor=c) for c in (0, 1))
+    assert (a["stage"], b["stage"]) == (1, 0)
+    assert 192 + 16 * 65 + 64 * 31 * 64 <= STAGE_LIMIT < 192 + 16 * 65 + 48 * 64 + 64 * 31 * 64
+
+
+def test_shape_lds_requests(shape):
+    """Every request is at least 82 KiB (one block per CU).  The look-back's terms (lb_final's region and
+    the waves' ranking lists, at most ~25 KB while nb_lb K stays near 640) and the peer exchange's (3024 B
+    per rank, 16 ranks at most) never pass that floor on their own: the model holds them, the total shows
+    the floor — test_ctl_shape shows both terms where no floor hides them.  The staged inputs and the
+    raceline's window do pass it."""
+    assert shape(256, None, n=97, la=1, C=3, H=12)["lds"] == ONE_BLOCK_PER_CU
+    assert lb_final_lds(20, 32) == 192 + 8 * 1940 + 16 * 80 + 4 * 1974 + 24 == 24912 < ONE_BLOCK_PER_CU
+    assert lb_final_lds(1, 1) == 192 + 4 * 1024 + 4 * 32 * 24 == 7360
+    assert shape(256, None, n=5120, lb=1, full=1, K=32)["lds"] == ONE_BLOCK_PER_CU
+    assert shape(256, None, n=5120, lb=1, full=0, K=32, la=1, C=3, H=12)["lds"] == ONE_BLOCK_PER_CU
+    for G in (2, 16):
+        assert 256 + G * (1488 + 1536) + 16 < ONE_BLOCK_PER_CU
+        s = shape(256, None, n=5120, lb=1, full=1, K=10, la=1, C=3, H=12, px_G=G)
+        assert (s["px"], s["lds"]) == (1, ONE_BLOCK_PER_CU)
+    s = shape(256, None, n=5120, lb=1, full=1, K=10, la=1, C=64, H=31, px_G=16)
+    assert (s["stage"], s["lds"]) == (1, 192 + 16 * 32 + 64 * 64 * 31)
+    # the raceline: 700 knots, 3 frictions: 50432 B of tables beside 10768 B of staged inputs leave room for
+    # 1058 segments of 96 B: the whole lap (699); 8 frictions (256 B per segment): 396 segments
+    rl = dict(n=97, la=1, C=8, H=20, xref_mode=XREF_RACELINE, rl_n=700)
+    a, b = shape(256, None, rl_M=3, **rl), shape(256, None, rl_M=8, **rl)
+    assert raceline_lds(700, 3) == 50432 and lookahead_lds(8, 20) == (10768, True)
+    assert (a["xm"], a["stage"], a["wcap"], a["lds"]) == (1, 1, 699, 10768 + 50432 + 96 * 699)
+    assert (b["wcap"], b["lds"]) == (396, 10768 + 50464 + 256 * 396) and b["lds"] <= PLAN_LDS_MAX
+    # inputs that are staged on their own but not beside the tables go unstaged
+    c = shape(256, None, rl_M=3, **dict(rl, C=64, H=31))
+    assert lookahead_lds(64, 31)[1] and (c["stage"], c["wcap"]) == (0, 699)
+
+
+@pytest.mark.parametrize("why,kw", [
+    ("corridor_rk6", dict(corridor=1, integrator=RK6)),
+    ("corridor_raceline", dict(corridor=1, xref_mode=XREF_RACELINE, rl_n=700, rl_M=3)),
+    ("corridor_inputs", dict(corridor=1, pack=1, H=2)),
+    ("corridor_inputs", dict(corridor=1, px_G=2)),
+    ("corridor_la", dict(corridor=1, la=0, lb=1, K=10)),
+    ("corridor_la", dict(corridor=1, la=0, C=-5, H=2 ** 31 - 1)),      # refused before any size is worked out
+    ("integrator", dict(corridor=1, integrator=7)),
+    ("integrator", dict(integrator=7)), ("integrator", dict(integrator=-1)),
+    ("pack", dict(pack=1, C=64, H=40)),
+    ("pack", dict(pack=1, C=8, H=40)),
+    ("pack", dict(pack=1, la=0, lb=1, K=10)),
+    ("pack", dict(pack=1, integrator=EULER_NLP, H=2)), ("pack", dict(pack=1, integrator=RK6, H=2)),
+    ("pack", dict(pack=1, xref_mode=XREF_RACELINE, rl_n=700, rl_M=3, H=2)),
+    ("peer", dict(px_G=17)),
+    ("peer", dict(px_G=2, integrator=EULER_NLP)), ("peer", dict(px_G=2, integrator=RK6)),
+    ("peer", dict(px_G=2, xref_mode=XREF_RACELINE, rl_n=700, rl_M=3)),
+    ("peer", dict(px_G=2, pack=1, H=2)),
+    ("work", dict(la=0)), ("work", dict(la=0, lb=1, n=0, K=10))])
+def test_shape_refusals(shape, why, kw):
+    got = shape(256, None, **dict(dict(n=97, la=1, C=3, H=12), **kw))
+    assert got["refuse"] == NO[why], (kw, got)
+
+
+def test_shape_accepts_what_it_should(shape):
+    """The neighbours of the refusals: each family's plain case, 16 ranks, the largest pack."""
+    base = dict(n=97, la=1, C=3, H=12)
+    for kw, family in ((dict(), PLAIN), (dict(corridor=1), CORRIDOR), (dict(corridor=1, integrator=EULER_NLP), CORRIDOR),
+                       (dict(pack=1), INLINE), (dict(px_G=16, lb=1, K=10), PLAIN), (dict(integrator=RK6), PLAIN),
+                       (dict(la=0, lb=1, K=10), PLAIN), (dict(pack=1, C=8, H=18), INLINE)):
+        s = shape(256, None, **dict(base, **kw))
+        assert s["refuse"] == "-" and s["family"] == family, (kw, s)
+    assert 16 + 2 * 19 + 2 * 8 * 18 <= INLINE_DOUBLES < 16 + 2 * 20 + 2 * 8 * 19
+    assert shape(256, None, **dict(base, pack=1, C=8, H=19))["refuse"] == NO["pack"]
+
+
+@pytest.mark.parametrize("K,n,R,nb_lb", [
+    (1, 32768, 1, 128), (1, 32769, 2, 65),        # 64 x 8 / 4 = 128 blocks at most per R step
+    (10, 16384, 1, 64), (10, 16385, 2, 33),       # 640 // 10 = 64 blocks
+    (32, 5120, 1, 20), (32, 5121, 2, 11),         # 640 // 32 = 20 blocks
+    (10, 1, 1, 1), (10, 256, 1, 1), (10, 257, 1, 2)])
+def test_shape_block_counts(shape, K, n, R, nb_lb):
+    for full in (0, 1):
+        s = shape(256, None, n=n, lb=1, full=full, K=K)
+        assert (s["R"], s["nb_lb"], s["nb_la"]) == (R, nb_lb, 0)
+    s = shape(256, {"LLAMPC_LB_R": "3"}, n=n, lb=1, K=K)
+    assert (s["R"], s["nb_lb"]) == (max(R, 3), cdiv(n, 256 * max(R, 3)))
+
+
+def test_plan_variant_entries_agree_with_shape(harness, nat, monkeypatch):
+    """llampc_plan_variant and llampc_plan_variant_corridor are plan_shape's (lpm, G, cpl, stage)."""
+    four = lambda s: dict(lpm=s["lpm"], G=s["G"], cpl=s["cpl"], stage=bool(s["stage"]))
+    for lpm_env in (None, "2"):
+        env = {"LLAMPC_LPM": lpm_env} if lpm_env else {}
+        monkeypatch.delenv("LLAMPC_LPM", raising=False)
+        if lpm_env:
+            monkeypatch.setenv("LLAMPC_LPM", lpm_env)
+        for n in (1, 257, 513, 10 ** 5):
+            for C_, H in ((1, 12), (3, 12), (31, 64), (64, 31), (64, 32), (65, 20), (130, 15), (257, 4)):
+                for integ in (RK4, EULER_NLP, RK6):
+                    for share in (1, 2):
+                        args = dict(n=n, la=1, C=C_, H=H, integrator=integ, share=share)
+                        got = parse_fields(harness("shape", 256, *(f"{k}={v}" for k, v in args.items()), env=env))
+                        assert nat.plan_variant(n, C_, H, integ, share) == four(got), (args, lpm_env)
+                        if integ != RK6:
+                            got = parse_fields(harness("shape", 256, "corridor=1", *(f"{k}={v}" for k, v in args.items()), env=env))
+                            assert nat.plan_variant_corridor(n, C_, H, integ, share) == four(got), (args, lpm_env)
+
+
+def ctl_lds_model(H, C, n, s4):
+    """ctl_lds.hpp: xref | U | knots + pad | two profiles | (s4) the staged terms | 1 KiB, 16-B aligned."""
+    a16 = lambda x: (x + 15) & ~15
+    o = a16(SCRATCH + 16 * (H + 1))
+    o = a16(o + 16 * C * H)
+    o = a16(o + 8 * (n + KNOT_PAD))
+    o = a16(o + 64 * (n - 1))
+    if s4:
+        o = a16(o + 16 * C * H + 16 * C)
+    return o + 1024
+
+
+def test_ctl_shape(harness, nat, monkeypatch):
+    """ctl_shape on the CPU: llampc_ctl_variant's nine fields are its own, and its LDS request is the
+    largest of the look-ahead layout, lb_final's region / the ranking lists and the exchange's region,
+    16-B aligned, plus the completing block's 4 KiB."""
+    monkeypatch.delenv("LLAMPC_CTL_NO_STAGE", raising=False)
+    ctl = lambda *a: parse_fields(harness("ctl_shape", *a))
+    for n, C_, H, K, rl_n in ((1, 1, 1, 1, 700), (200, 8, 20, 10, 700), (10000, 64, 40, 10, 700), (100, 128, 25, 5, 700),
+                              (50, 300, 10, 3, 500), (5121, 8, 10, 32, 700), (16385, 8, 10, 10, 700), (100, 96, 20, 10, 700)):
+        got = ctl(n, C_, H, K, rl_n, 0, 1, 0, 0)
+        assert nat.ctl_variant(n, C_, H, K, rl_n) == {f: got[f] for f in nat.CTL_VARIANT_FIELDS}, (n, C_, H, K, rl_n)
+        assert got["nslots"] == K + 1
+        want = max(ctl_lds_model(H, C_, rl_n, got["s4"]), lb_final_lds(got["nb_lb"], K))
+        assert (got["poll_off"], got["lds"]) == (want, want + 4096)
+    # a tiny look-ahead on a two-knot track: the ranking lists (7360 B), then lb_final's region at 20 blocks
+    # of K = 32 (24912 B), then the exchange of 16 ranks (192 + 8448 + 8192 + 144 B)
+    assert ctl_lds_model(1, 1, 2, True) == 1440
+    assert ctl(1, 1, 1, 1, 2, 0, 1, 0, 0)["poll_off"] == 7360
+    assert ctl(5120, 1, 1, 32, 2, 0, 1, 0, 0)["poll_off"] == 24912
+    assert ctl(1, 1, 1, 32, 2, 0, 1, 0, 16)["poll_off"] == 192 + 4 * 16 * 4 * 33 + 16 * 16 * 32 + 4 * 32 + 16 == 16976
+    # warm-up ticks roll one model out; without a look-back one block completes; no_stage drops s4 alone
+    w = ctl(200, 8, 20, 10, 700, 1, 0, 0, 0)
+    assert (w["nslots"], w["nb_la"], w["nb_lb"]) == (1, 1, 1)
+    a, b = ctl(100, 96, 20, 10, 700, 0, 1, 0, 0), ctl(100, 96, 20, 10, 700, 0, 1, 1, 0)
+    assert a["s4"] == 1 and b["s4"] == 0 and b["lds"] < a["lds"] and {**a, "s4": 0, "lds": 0, "poll_off": 0} == {**b, "lds": 0, "poll_off": 0}
