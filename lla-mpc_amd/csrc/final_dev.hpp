@@ -101,6 +101,12 @@ __device__ __forceinline__ void lb_final(const FinalLaunch& f, unsigned char* sm
     const double v = ld_wt(&f.tk_val[e]);
     const uint32_t l = local(ld_wt(&f.tk_idx[e]));
     const uint64_t k = l == kNoLocal ? ~0ull : order_key(v);
+    // e >= 512 (M up to 640): the id wraps past 2^32 to e - 512.  It stays unique among the missing
+    // entries (M < 2^32) and never reaches the output: only missing entries carry key ~0 (a NaN's
+    // key is below it) and M > 512 takes L >= 17 blocks, so more than 4096 >= K models: the K
+    // entries top[] names are real ones, which rank below every missing one under (key, id), and the
+    // `id >= kNoModelId` test below is never asked about a wrapped id
+    // (tests/test_lookback_matrix_gpu.py, the n4869-k32 rows: M = 640, 27 missing entries at e >= 613).
     const uint32_t i = l == kNoLocal ? kNoModelId + (uint32_t)e : l;
     key[e] = k;
     val[e] = v;

@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from lookback_matrix import SHAPE_ROWS as LOOKBACK_MATRIX_SHAPES
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 INT32_MAX, UINT32_MAX, U64_MAX = 2 ** 31 - 1, 2 ** 32 - 1, 2 ** 64 - 1
@@ -484,11 +486,16 @@ def test_shape_accepts_what_it_should(shape):
     assert shape(256, None, **dict(base, pack=1, C=8, H=19))["refuse"] == NO["pack"]
 
 
-@pytest.mark.parametrize("K,n,R,nb_lb", [
+SHAPE_BLOCK_ROWS = [
     (1, 32768, 1, 128), (1, 32769, 2, 65),        # 64 x 8 / 4 = 128 blocks at most per R step
     (10, 16384, 1, 64), (10, 16385, 2, 33),       # 640 // 10 = 64 blocks
     (32, 5120, 1, 20), (32, 5121, 2, 11),         # 640 // 32 = 20 blocks
-    (10, 1, 1, 1), (10, 256, 1, 1), (10, 257, 1, 2)])
+    (10, 1, 1, 1), (10, 256, 1, 1), (10, 257, 1, 2)]
+# + the look-back matrix's stated (K, N, R, L), those not already above (two are: the same ids)
+SHAPE_BLOCK_ROWS += [r for r in LOOKBACK_MATRIX_SHAPES if r not in SHAPE_BLOCK_ROWS]
+
+
+@pytest.mark.parametrize("K,n,R,nb_lb", SHAPE_BLOCK_ROWS)
 def test_shape_block_counts(shape, K, n, R, nb_lb):
     for full in (0, 1):
         s = shape(256, None, n=n, lb=1, full=full, K=K)
