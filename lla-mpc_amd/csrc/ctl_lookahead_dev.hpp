@@ -243,7 +243,7 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
   const bool diagQP = c.la.cost.Q[1] == 0.0 && c.la.cost.Q[2] == 0.0 && c.la.cost.P[1] == 0.0 && c.la.cost.P[2] == 0.0;
   if (live) {
     constexpr bool kScaled = scaled_yaw(LPM);
-    StageK sk = make_stage<LPM>(veh, t, sub, Ts);
+    StageK sk = make_stage<LPM>(veh, t, sub, Ts, Ts * veh.inv_mass);   // the quad's rear lane: (h/m) Fry
     if (kScaled) sk.ch[0].lw = sk.ch[0].lw / Ts;
     if (kScaled && LPM == 1) sk.ch[1].lw = sk.ch[1].lw / Ts;
     if (kScaled && LPM == 4 && sub >= 2) {   // lanes 2/3: zero-operand chains (plan kernel)
@@ -251,8 +251,9 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
       sk.ch[0].sg = 0.0;
       sk.ch[0].B = 0.0;
       sk.ch[0].nsB = 0.0;
+      sk.Bfw = 0.0;
     }
-    const FusedK fq = make_fused(veh, sk, Ts, kScaled);
+    const FusedK fq = make_fused(veh, sk, Ts, kScaled, LPM == 4);
     const fm::FmK K = load_la_consts<0, LPM>();
     for (int j = 0; j < cpl; ++j) {
       const int cc = g + j * G;

@@ -187,15 +187,16 @@ __device__ __forceinline__ void ctl_spec(const CtlLaunch& c, int j, unsigned cha
     pin_vgpr(veh.Cr2);
     pin_vgpr(Ts);
     constexpr bool kScaled = scaled_yaw(LPM);
-    StageK sk = make_stage<LPM>(veh, t, sub, Ts);
+    StageK sk = make_stage<LPM>(veh, t, sub, Ts, Ts * veh.inv_mass);   // the quad's rear lane: (h/m) Fry
     if (kScaled) sk.ch[0].lw = sk.ch[0].lw / Ts;
     if (kScaled && sub >= 2) {          // lanes 2/3: zero-operand chains (plan kernel)
       sk.ch[0].lw = 0.0;
       sk.ch[0].sg = 0.0;
       sk.ch[0].B = 0.0;
       sk.ch[0].nsB = 0.0;
+      sk.Bfw = 0.0;
     }
-    const FusedK fq = make_fused(veh, sk, Ts, kScaled);
+    const FusedK fq = make_fused(veh, sk, Ts, kScaled, LPM == 4);
     const fm::FmK K = load_la_consts<0, LPM>();
     const double Qd = sk.pc ? q.Q[3] : q.Q[0], Pd = sk.pc ? q.P[3] : q.P[0];
     // cpl == 1 with G == C (the host's layout for spec blocks): candidate g in quad g

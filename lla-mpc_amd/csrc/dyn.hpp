@@ -336,33 +336,49 @@ __device__ __forceinline__ void chain_pair(const Chain& cf, const Chain& cr, dou
 // LPM = 4: the quad's lanes run ONE instruction stream — lanes 0/1 the front/rear chain,
 // lanes 2/3 the same chains (wasted) up to the final sine, whose argument is theirs:
 // lane 2 sin(psi), lane 3 cos(psi), so sincos(psi) costs no polynomial of its own.
-// psi = r + k pi (2k = nearest even integer to psi 2/pi, 3-part Cody-Waite by pi/2, |r| <=
-// pi/2); sin psi = sin((-1)^k r), cos psi = sin((-1)^k (pi/2 - |r|)).  Per lane:
-// c.C = C (lanes 0/1) or 0 (2/3), c.D = D or 1, ra = the |r| mask of the high word (lane 3
-// clears the sign), pm = 0 / 1 / -1 and po = 0 / 0 / pi/2 place the angle argument
+// Unscaled (the NLP-Euler quad): psi = r + k pi (2k = nearest even integer to psi 2/pi, 3-part
+// Cody-Waite by pi/2, |r| <= pi/2); sin psi = sin((-1)^k r), cos psi = sin((-1)^k (pi/2 - |r|)).
+// Per lane: c.C = C (lanes 0/1) or 0 (2/3), c.D = D or 1, ra = the |r| mask of the high word
+// (lane 3 clears the sign), pm = 0 / 1 / -1 and po = 0 / 0 / pi/2 place the angle argument
 // po + pm r' (exactly 0 in lanes 0/1, so their argument is C atan(.) as at LPM 1/2).
-// SCALED: psi arrives as Psi = (2/pi) psi (the fused quad's state, step_fused): k2 = the
-// even integer nearest Psi, r = (Psi - k2) pi/2 — the subtraction is exact (|Psi| < 2^51),
-// so the fold is 4 instructions instead of the 3-part Cody-Waite's 5.
-template <bool SCALED = false, bool LEAN = false>
+// SCALED: psi arrives as Psi = (2/pi) psi (the fused quad's state, step_fused), and lane 3
+// carries Psi + 1 — an exact quarter turn in these units (rollout_dev.hpp rollout), so
+// cos psi = sin(pi/2 (Psi + 1)) is lane 2's fold on lane 3's own state: k2 = the even integer
+// nearest the lane's Psi, d = Psi - k2 (exact: |Psi| < 2^51), r = d pq with the per-lane
+// pq = pi/2 on lanes 2/3 and 0 on lanes 0/1 (their argument stays +-0: C atan(.) as before),
+// and sin(pi/2 Psi) = sin((-1)^k r).  Six instructions: no |r| mask, no pi/2 - |r|, none
+// of ra / pm / po.  Psi = an odd integer is a tie of k2 either way: d = +-1, r = +-pi/2 with
+// the parity that goes with it, the same sine.
+// YAW1 = false (the raceline kernels, rollout_dev.hpp): every lane carries Psi itself and the
+// scaled fold forms lane 3's pi/2 - |r| with ra / pm / po as the unscaled one does (with the
+// shorter fold the staged raceline kernel takes a private segment).
+template <bool SCALED = false, bool LEAN = false, bool YAW1 = true>
 __device__ __forceinline__ double chain_fold(const Chain& c, double den, double vy, double om,
                                              double Bd, double psi, int ra, double pm,
-                                             double po, Dom& dm, const fm::FmK& K) {
-  double t2, r;
+                                             double po, double pq, Dom& dm, const fm::FmK& K) {
+  double t2, pa;
   if constexpr (SCALED) {
     t2 = psi + K.rmagic2;                                // 2^53 (1.5 + 2k 2^-53): ulp 2
     const double k2 = t2 - K.rmagic2;
-    r = (psi - k2) * K.pio2;
+    if constexpr (YAW1) {
+      pa = (psi - k2) * pq;
+    } else {
+      const double r = (psi - k2) * K.pio2;
+      const double rr = __hiloint2double(__double2hiint(r) & ra, __double2loint(r));
+      pa = fma(pm, rr, po);
+    }
   } else {
     t2 = fma(psi, K.two_pi, K.rmagic2);
     const double k2 = t2 - K.rmagic2;
-    r = fma(-k2, K.cw0, psi);
+    double r = fma(-k2, K.cw0, psi);
     r = fma(-k2, K.cw1, r);
     r = fma(-k2, K.cw2, r);
+    const double rr = __hiloint2double(__double2hiint(r) & ra, __double2loint(r));
+    pa = fma(pm, rr, po);
   }
-  const double rr = __hiloint2double(__double2hiint(r) & ra, __double2loint(r));
-  const double pa = fma(pm, rr, po);
-  const int fs = __double2loint(t2) << 31;               // (-1)^k on the argument
+  // (-1)^k on the argument.  (hi + (lo(t2) << 31) is the same word in one v_lshl_add_u32;
+  // the tick was slower with it in six of six pairs)
+  const int fs = __double2loint(t2) << 31;
   const double arg_psi = __hiloint2double(__double2hiint(pa) ^ fs, __double2loint(pa));
   double at;
   {
@@ -383,24 +399,33 @@ __device__ __forceinline__ double chain_fold(const Chain& c, double den, double 
 struct StageK {
   Chain ch[2];
   double fw;
+  double Bfw;              // B fw, the steering term's factor: Bd = Bfw delta (step_fused)
   double k1, k2, k0, k3;   // Frx = (k1 - k2 vx) a - k0 - k3 vx^2; input_acc: (mass, 0, 0, 0)
-  double pm, po;           // LPM = 4: the angle argument of chain_fold
+  double pm, po;           // LPM = 4: the angle argument of chain_fold (unscaled)
+  double pq;               // LPM = 4: pi/2 on lanes 2/3, 0 on lanes 0/1 (chain_fold<SCALED>)
   double psg;              // LPM = 4 position split: -1 on X lanes, +1 on Y lanes
   int ra;
   int pc;                  // LPM = 4 position split: the lane's component (0 = X, 1 = Y)
+  bool l3;                 // LPM = 4: quad lane 3, whose scaled yaw state is Psi + 1 (rollout)
   bool sok;
 };
 
 // psi_scale: LPM = 4 lanes 2/3 return psi_scale sin(psi), psi_scale cos(psi) (the fused RK4
 // passes h, so the stage increments need no h vx, h vy products).
+// rear_scale: LPM = 4 lane 1 returns rear_scale Fry (the fused RK4 passes h/m: k_fused takes
+// the product as it comes, make_fused(.., rear_hm = true) divides hIlr by it).  The static
+// domain is judged on the tire's own D.
 template <int LPM>
 __device__ __forceinline__ StageK make_stage(const VehK& v, const Tire& t, int sub,
-                                             double psi_scale = 1.0) {
+                                             double psi_scale = 1.0, double rear_scale = 1.0) {
   const bool front = (LPM == 1) || (sub & 1) == 0;
   StageK s;
   s.ch[0] = make_chain(v, t, front);
   s.ch[1] = make_chain(v, t, false);
   s.fw = front ? 1.0 : 0.0;
+  s.Bfw = s.ch[0].B * s.fw;
+  s.pq = (LPM == 4 && sub >= 2) ? fm::kPio2 : 0.0;
+  s.l3 = LPM == 4 && sub == 3;
   s.pm = sub == 2 ? 1.0 : (sub == 3 ? -1.0 : 0.0);
   s.po = sub == 3 ? fm::kPio2 : 0.0;
   s.ra = sub == 3 ? 0x7FFFFFFF : -1;
@@ -419,6 +444,7 @@ __device__ __forceinline__ StageK make_stage(const VehK& v, const Tire& t, int s
     // (their atan2 / atan duplicate lanes 0/1's chains; constant operands there instead
     // — yy = z = 0 — clocked 1.5 % higher but took 4.5 % more cycles)
   }
+  if (LPM == 4 && sub == 1) s.ch[0].D = s.ch[0].D * rear_scale;
   return s;
 }
 
@@ -426,18 +452,18 @@ __device__ __forceinline__ StageK make_stage(const VehK& v, const Tire& t, int s
 struct StageF {
   double Ffy, Fry, sp, cp;
 };
-// Bd = B d fw, the chain's steering term (LPM = 4 only; formed once per step).
+// Bd = (B fw) d, the chain's steering term (LPM = 4 only; formed once per step).
 // POS (LPM = 4): kPosSplit — sp/cp carry the split's A/B operands instead (X lanes: cos, sin;
 // Y lanes: sin, cos — kQuadPosA/B); kPosQuadr — sp is the lane's own chain result (lanes 0/1
 // their force, lane 2 h sin psi, lane 3 h cos psi), cp is unused: two broadcasts, not four.
-template <int LPM, int POS = kPosBoth, bool SCALED = false, bool LEAN = false>
+template <int LPM, int POS = kPosBoth, bool SCALED = false, bool LEAN = false, bool YAW1 = true>
 __device__ __forceinline__ StageF forces_fast(const StageK& sk, double den, double vy, double om,
                                               double d, double psi, const fm::FmK& K, Dom& dm,
                                               double Bd = 0.0) {
   StageF f;
   dm.ps = fm::vmax_abs(psi, dm.ps);
   if (LPM == 4) {
-    const double r = chain_fold<SCALED, LEAN>(sk.ch[0], den, vy, om, Bd, psi, sk.ra, sk.pm, sk.po, dm, K);
+    const double r = chain_fold<SCALED, LEAN, YAW1>(sk.ch[0], den, vy, om, Bd, psi, sk.ra, sk.pm, sk.po, sk.pq, dm, K);
     f.Ffy = quad_bcast<kQuad0, 0>(r);
     f.Fry = quad_bcast<kQuad1, 1>(r);
     if constexpr (POS == kPosQuadr) {
@@ -535,7 +561,9 @@ __device__ __forceinline__ Input make_input_fast(double a, double d, const fm::F
 // per step with the position split, 440 with the position quadrature (step_fused
 // kPosQuadr, round 8: -4 fp64, -14 DPP moves, -3 s_nop) and 418 with the one-select octant
 // fix-up and the three-zone lean atan (fastmath.hpp octant_fix / atan_zones, round 9:
-// 2,132 -> 2,000 cycles per step).
+// 2,132 -> 2,000 cycles per step), and 406 with lane 3 on Psi + 1 (chain_fold<SCALED>: -4 FMA,
+// -4 v_and), B fw per rollout (-1 mul) and h/m in the rear lane's D (make_stage rear_scale:
+// -4 mul; round 10: 2,000 -> 1,968 cycles per step, 24.1 -> 23.6 us per tick).
 constexpr bool kLeanLA = true;
 // The FmK of a look-ahead rollout: the lean coefficient sets under the fused RK4 (INTEG 0), and
 // atan_zones' constants and the select words pinned where the lanes take them (fm::chain_selects).
@@ -562,8 +590,11 @@ constexpr bool scaled_yaw(int lpm) {
 // takes one more factor h (hIlf, hIlr), the chains' lw / h turns W back into omega for the
 // slip angles, and the yaw's RK4 weights carry 2/pi (FmK inv_pi, two_pi, inv_3pi) — the
 // fold then needs no Cody-Waite (chain_fold<true>).  Same arithmetic up to roundings.
+// rear_hm (the quad): the rear lane's chain returns (h/m) Fry (make_stage rear_scale = h *
+// inv_mass, the same product as hm), so k4 takes it without a product and hIlr is divided by
+// hm for k5 — one multiplication per stage less, other roundings of vy and omega.
 __device__ __forceinline__ FusedK make_fused(const VehK& v, const StageK& sk, double h,
-                                             bool scaled = false) {
+                                             bool scaled = false, bool rear_hm = false) {
   FusedK q;
   q.h = h;
   q.hm = h * v.inv_mass;
@@ -573,6 +604,7 @@ __device__ __forceinline__ FusedK make_fused(const VehK& v, const StageK& sk, do
     q.hIlf *= h;
     q.hIlr *= h;
   }
+  if (rear_hm) q.hIlr = q.hIlr / q.hm;
   q.m1 = q.hm * sk.k1;
   q.m0 = q.hm * sk.k0;
   q.m2 = q.hm * sk.k2;
@@ -587,13 +619,13 @@ __device__ __forceinline__ FusedK make_fused(const VehK& v, const StageK& sk, do
 // POS = kPosQuadr: no position increment here at all — k[0] returns the lane's own chain
 // result r and step_fused sums vy r and vx r over the stages (the position is a quadrature of
 // what the lanes already hold: it feeds no stage).
-template <int LPM, int POS = kPosBoth>
+template <int LPM, int POS = kPosBoth, bool YAW1 = true>
 __device__ __forceinline__ void k_fused(const StageK& sk, const FusedK& q, double F0, double F1,
                                         double hmsd, double hmcd, double c5a, double d, double Bd,
                                         const double* y, double* k, const fm::FmK& K, Dom& dm) {
   const double vx = y[3], vy = y[4], om = y[5];
   constexpr bool kScaled = scaled_yaw(LPM);   // om = W = h omega, y[2] = Psi (make_fused)
-  const StageF f = forces_fast<LPM, POS, kScaled, kLeanLA>(sk, vx, vy, om, d, y[2], K, dm, Bd);
+  const StageF f = forces_fast<LPM, POS, kScaled, kLeanLA, YAW1>(sk, vx, vy, om, d, y[2], K, dm, Bd);
   // h sin(psi), h cos(psi): LPM = 4 lanes 2/3 scale their sine by h already (make_stage)
   const double hsp = (LPM == 4) ? f.sp : q.h * f.sp, hcp = (LPM == 4) ? f.cp : q.h * f.cp;
   const double hmFrx = fma(vx, fma(q.m3, vx, F1), F0);                     // hm Frx
@@ -609,7 +641,9 @@ __device__ __forceinline__ void k_fused(const StageK& sk, const FusedK& q, doubl
     k[1] = fma(vx, hsp, vy * hcp);
   }
   k[3] = fma(-f.Ffy, hmsd, fma(vy, k[2], hmFrx));                         // h/m (Frx - Ffy sd) + h vy om
-  k[4] = fma(f.Ffy, hmcd, fma(-vx, k[2], q.hm * f.Fry));                  // h/m (Fry + Ffy cd) - h vx om
+  // LPM = 4: f.Fry is (h/m) Fry already and q.hIlr = hIlr / hm (make_fused rear_hm)
+  const double hmFry = (LPM == 4) ? f.Fry : q.hm * f.Fry;
+  k[4] = fma(f.Ffy, hmcd, fma(-vx, k[2], hmFry));                         // h/m (Fry + Ffy cd) - h vx om
   k[5] = fma(f.Ffy, c5a, -(f.Fry * q.hIlr));                              // h/Iz (Ffy lf cd - Fry lr)
 }
 
@@ -634,7 +668,7 @@ __device__ __forceinline__ FusedIn fused_in(const FusedK& q, const Input& u) {
 // (rollout_dev.hpp takes the tracking terms of lanes 2 and 3 only).  The sums' order differs
 // from kPosSplit's per-stage increments: ~1 ulp per step on the positions; velocities, yaw
 // and the domain record are the same instructions on the same operands.
-template <int LPM, int POS = kPosBoth>
+template <int LPM, int POS = kPosBoth, bool YAW1 = true>
 __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, double* x,
                                            const FusedIn& fi, double ud, const fm::FmK& K,
                                            Dom& dm) {
@@ -642,11 +676,12 @@ __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, do
   constexpr bool SPLIT = POS != kPosBoth, QUADR = POS == kPosQuadr;
   const double F0 = fi.F0, F1 = fi.F1, hmsd = fi.hmsd, hmcd = fi.hmcd, c5a = fi.c5a;
   const Input u{0.0, ud, 0.0, 0.0};                       // k_fused reads u.d only
-  const double Bd = (LPM == 4) ? sk.ch[0].B * (u.d * sk.fw) : 0.0;
+  // (B fw) d: fw is exactly 0 or 1, so the bits of B (d fw), signed zeros and NaN included
+  const double Bd = (LPM == 4) ? sk.Bfw * u.d : 0.0;
   double y[6], k[6], acc[6];
   y[1] = acc[1] = 0.0;
   [[maybe_unused]] double P = 0.0, G = 0.0, Pm = 0.0, Gm = 0.0;            // QUADR: the stage sums
-  k_fused<LPM, POS>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, x, k, K, dm);
+  k_fused<LPM, POS, YAW1>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, x, k, K, dm);
   if constexpr (QUADR) {
     P = x[4] * k[0];
     G = x[3] * k[0];
@@ -661,7 +696,7 @@ __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, do
     acc[i] = k[i];
     y[i] = fma(i == 2 ? c2 : 0.5, k[i], x[i]);
   }
-  k_fused<LPM, POS>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  k_fused<LPM, POS, YAW1>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
   if constexpr (QUADR) {
     Pm = y[4] * k[0];
     Gm = y[3] * k[0];
@@ -672,7 +707,7 @@ __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, do
     acc[i] = fma(2.0, k[i], acc[i]);
     y[i] = fma(i == 2 ? c2 : 0.5, k[i], x[i]);
   }
-  k_fused<LPM, POS>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  k_fused<LPM, POS, YAW1>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
   if constexpr (QUADR) {
     Pm = fma(y[4], k[0], Pm);
     Gm = fma(y[3], k[0], Gm);
@@ -683,7 +718,7 @@ __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, do
     acc[i] = fma(2.0, k[i], acc[i]);
     y[i] = (i == 2 && kScaled) ? fma(c4, k[i], x[i]) : x[i] + k[i];
   }
-  k_fused<LPM, POS>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
+  k_fused<LPM, POS, YAW1>(sk, q, F0, F1, hmsd, hmcd, c5a, u.d, Bd, y, k, K, dm);
   if constexpr (QUADR) {
     P = fma(2.0, Pm, fma(y[4], k[0], P));
     G = fma(2.0, Gm, fma(y[3], k[0], G));
@@ -696,10 +731,10 @@ __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, do
   }
 }
 
-template <int LPM, int POS = kPosBoth>
+template <int LPM, int POS = kPosBoth, bool YAW1 = true>
 __device__ __forceinline__ void step_fused(const StageK& sk, const FusedK& q, double* x,
                                            const Input& u, const fm::FmK& K, Dom& dm) {
-  step_fused<LPM, POS>(sk, q, x, fused_in(q, u), u.d, K, dm);
+  step_fused<LPM, POS, YAW1>(sk, q, x, fused_in(q, u), u.d, K, dm);
 }
 
 // One look-ahead step on the fast path.

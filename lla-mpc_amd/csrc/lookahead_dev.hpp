@@ -270,7 +270,8 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
   StageK sk;
   FusedK fq;
   auto model_setup = [&] {
-    sk = make_stage<LPM>(veh, t, sub, INTEG == 0 ? Ts : 1.0);
+    // fused RK4 quads: lanes 2/3 return h sin / h cos psi, the rear lane (h/m) Fry (make_fused rear_hm)
+    sk = make_stage<LPM>(veh, t, sub, INTEG == 0 ? Ts : 1.0, INTEG == 0 ? Ts * veh.inv_mass : 1.0);
     if (kScaled) sk.ch[0].lw = sk.ch[0].lw / Ts;
     if (kScaled && LPM == 1) sk.ch[1].lw = sk.ch[1].lw / Ts;
     if (kScaled && LPM == 4 && sub >= 2) {
@@ -281,8 +282,9 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
       sk.ch[0].sg = 0.0;
       sk.ch[0].B = 0.0;
       sk.ch[0].nsB = 0.0;
+      sk.Bfw = 0.0;
     }
-    fq = make_fused(veh, sk, Ts, kScaled);
+    fq = make_fused(veh, sk, Ts, kScaled, INTEG == 0 && LPM == 4);
   };
   // Shared xref: ONE FmK for the staging below and the rollouts (the staging uses its sincos
   // constants, the same in the lean and precise sets) instead of materialising the ~50

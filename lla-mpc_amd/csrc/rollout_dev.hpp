@@ -118,6 +118,7 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
   constexpr bool TRAJ = F & kRTraj, S4 = F & kRS4, DEFER = F & kRDefer, CORR = F & kRCorr, QUADR = F & kRQuadr;
   constexpr int POS = QUADR ? kPosQuadr : (SPLIT ? kPosSplit : kPosBoth);   // dyn.hpp step_fused
   constexpr int XM = (F & kRXm) ? 1 : 0;
+  constexpr bool kYaw1 = !XM;           // the quad's lane 3 carries Psi + 1 (below; dyn.hpp chain_fold)
   static_assert(!DEFER || (SPLIT && S4), "deferred tracking cost: the controller's split, staged rollout");
   static_assert(!TRAJ || (INTEG != 0 && !SPLIT), "trajectory output: unscaled, unsplit state");
   static_assert(!S4 || (ULDS && FAST && !STAGE), "staged sincos / cost terms: the controller's fast rollout");
@@ -135,6 +136,12 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
   if (FAST && INTEG == 0 && scaled_yaw(LPM)) {   // the scaled yaw and yaw rate (make_fused)
     x[2] = x0[2] * K.two_pi;
     x[5] = x0[5] * Ts;
+    // The quad's lane 3 carries Psi + 1, a quarter turn: its fold is then lane 2's and returns
+    // cos psi (dyn.hpp chain_fold<SCALED>).  A lane's Psi is read by its own fold and by dm.ps
+    // only — the yaw increment is W, the cost takes positions, no variant stores or broadcasts
+    // x[2] (TRAJ is unscaled) — so the offset ends there; dm.ps of lane 3 is max |Psi + 1|, one
+    // unit early at the fold's range, and the general re-run starts again from x0.
+    if (LPM == 4 && kYaw1) x[2] = sk.l3 ? x[2] + 1.0 : x[2];
   }
   const double Qd = sk.pc ? q.Q[3] : q.Q[0], Pd = sk.pc ? q.P[3] : q.P[0];   // SPLIT only
   double track = 0.0, act = 0.0;
@@ -190,8 +197,8 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
     }
     const double d0 = ua - p0, d1 = ud - p1;          // nmpc.py:65-68
     if (!STAGE && !S4 && q.enforce) feas = (int)feas & (int)input_feasible(q, ua, ud, d0, d1);
-    if (FAST && INTEG == 0 && STAGE) step_fused<LPM, POS>(sk, fq, x, fi, ud, K, dm);
-    else if (FAST && INTEG == 0) step_fused<LPM, POS>(sk, fq, x, u, K, dm);
+    if (FAST && INTEG == 0 && STAGE) step_fused<LPM, POS, kYaw1>(sk, fq, x, fi, ud, K, dm);
+    else if (FAST && INTEG == 0) step_fused<LPM, POS, kYaw1>(sk, fq, x, u, K, dm);
     else if (FAST) step_fast<INTEG, LPM>(veh, t, sk, x, u, Ts, K, dm);
     else step<INTEG>(veh, t, x, u, Ts);
     if constexpr (CORR) pen = pen + corridor_slack2(hp + 6 * k, x[0], x[1]);
