@@ -455,6 +455,44 @@ int llampc_ctl_reference(llampc_ctl* ctl, const double* x0, double v0, int32_t H
                          double scale, double* xref, int32_t* projidx_out, double* vr);
 /* The last tick's reference xref [2][H+1] and candidates U [C][H][2] (cfg.debug_inputs = 1). */
 int llampc_ctl_inputs(llampc_ctl* ctl, double* xref, double* U);
+/* ---- the soft track corridor inside the controller tick ----
+ * The reference's constraints.py (Boundary(): the track's boundary lines linearised per step, with
+ * slack variables in the NLP of nmpc.py:161-203) as a soft term of the candidate search: every
+ * rolled-out (model, candidate) cost becomes J + weight x the summed squared slacks of the rollout's
+ * positions on per-step half-planes hp_t [H][6] (llampc_plan_corridor's term).  hp_t is the track's
+ * corridor (llampc.mpc.constraints.track_corridor, half width track_width / 2 - margin) along the
+ * PREVIOUS tick's chosen rollout shifted one step (constraints.default_path's prev_xmpc rule), built
+ * by H corridor blocks inside the tick's one launch; tick 0, the first tick after the corridor is
+ * switched on and a tick after a non-finite chosen rollout use constraints.disabled(H).  Nothing in
+ * hp_t depends on x_t.  The record, the reference, the candidates, the look-back, the selection and
+ * mu-hat are unchanged; corridor ticks run the unstaged, unsplit look-ahead without speculative blocks.
+ *
+ * llampc_ctl_set_track: the centre line as llampc_nlp_set_track takes it (centre [2][n], theta [n]
+ * from 0 strictly increasing, track_length > theta[n-1], track_width > 0; the same refusals,
+ * LLAMPC_E_ARG).  LLAMPC_E_STATE with a tick outstanding or the corridor on.  Blocking. */
+int llampc_ctl_set_track(llampc_ctl* ctl, const double* centre /* [2][n] */, const double* theta /* [n] */, int32_t n,
+                         double track_length, double track_width);
+/* weight > 0: the next ticks are corridor ticks; weight 0: off — the path state is invalidated and
+ * the controller launches the plain tick again, its records those of a controller that never had a
+ * corridor.  Cancels an armed launch first.  LLAMPC_E_STATE: no track set, a tick outstanding, or a
+ * sharded controller (llampc_ctl_set_exchange / llampc_ctl_set_gather, which in turn refuse a
+ * controller whose corridor is on).  LLAMPC_E_ARG: a weight that is negative or not finite, a margin
+ * that is not finite or >= track_width / 2, a shape whose corridor tick exceeds the LDS.  Nothing is
+ * enqueued either way. */
+int llampc_ctl_set_corridor(llampc_ctl* ctl, double weight, double margin);
+/* The last tick's corridor: the path P [2][H+1] it was built along (NaN when invalid), hp [H][6],
+ * the path points' arc lengths theta [H] (NaN when invalid) and whether the path was valid.
+ * Blocking, as llampc_ctl_inputs; LLAMPC_E_STATE unless the last tick was a corridor tick. */
+int llampc_ctl_corridor(llampc_ctl* ctl, double* path, double* hp, double* theta, int32_t* valid);
+/* Every rolled-out cost of the last corridor tick (cfg.debug_inputs = 1, for tests: the record carries
+ * each slot's best alone): costs [nslots][C] in the record's slot order — while warm the nominal
+ * model's one slot, else the top-K's K slots and then the selection's; a slot without a model is NaN.
+ * Blocking, as llampc_ctl_inputs; LLAMPC_E_STATE without debug_inputs or a last corridor tick. */
+int llampc_ctl_corridor_costs(llampc_ctl* ctl, double* costs /* [K + 1][C] */, int32_t* nslots);
+/* llampc_ctl_variant for a corridor tick on a centre line of track_n points (host only): its nine
+ * fields (s4 = 0), then the corridor block count (H). */
+int llampc_ctl_variant_corridor(int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl_n, int32_t track_n,
+                                int32_t out[10]);
 /* The controller over a bank SHARDED across ranks (BASELINE config 5: one process per GPU, each
  * rank's controller on its contiguous shard; replaces the single-process loop rt.py:269-366 with
  * its look-back over the whole bank).  Call on every rank before the first tick: `mb` is this

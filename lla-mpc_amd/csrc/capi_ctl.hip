@@ -70,7 +70,20 @@ struct __attribute__((visibility("hidden"))) llampc_ctl {
   uint32_t door_ctr = 0;                 // never reused: a cancelled word cannot match a later launch
   uint64_t dev_ticks = 0;                // the last completed tick's device time (llampc_ctl_device_us)
   std::chrono::steady_clock::time_point arm_t{};
+  // the soft track corridor (llampc_ctl_set_track / llampc_ctl_set_corridor; ctl.hpp CtlCorridor)
+  DevBuf<double> d_track;                // cx | cy | tt, [3][tr_n]
+  int32_t tr_n = 0;                      // 0: no track set
+  double tr_L = 0.0, tr_width = 0.0;
+  double cor_w = 0.0, cor_margin = 0.0;  // weight 0: off (the tick launches ctl_kernel)
+  bool cor_prev = false;                 // the last tick enqueued was a corridor tick (CtlCorridor.path_ok)
+  DevBuf<double> d_cor;                  // path state [2][2][HMAX + 1], then the read-back copies [2][kCtlCorDbgDoubles]
+  DevBuf<uint64_t> d_hp_tag;             // [12 HMAX]
+  DevBuf<int32_t> d_cor_flag;            // the paths' valid flags [2], the read-back's [2]
+  DevBuf<double> d_cor_cost;             // debug_inputs: every rolled-out cost of the last corridor tick [kCtlSlotsMax][C]
+  int32_t cor_nslots = 0;                //   and how many slots it rolled out
   struct Prep {                          // a prepared tick: its launch and what it commits
+    bool corr = false;                   // a corridor tick: ctl_kernel_corr with `cor`
+    CtlCorridor cor{};
     CtlLaunch L{};
     int lpm = 4;
     size_t lds = 0;
@@ -352,7 +365,10 @@ static int ctl_prepare(llampc_ctl* c, const double* x_t, llampc_ctl::Prep& P) {
     L.px_bound = 16;                     // ~10 ms: the records are there when the launch starts
   }
   // the launch's shape (capi_host.hpp ctl_shape: the lane split, the staging, the block counts)
-  const CtlShape V = ctl_shape(b->n, k.C, k.H, k.K, b->rl_n, warm, do_lb, c->no_stage, L.px_G);
+  // a corridor tick (llampc_ctl_set_corridor, weight > 0): ctl_kernel_corr — never staged, H corridor
+  // blocks, no speculative blocks (L.s4 = 0 rules them out below)
+  const bool corr = c->cor_w > 0;
+  const CtlShape V = ctl_shape(b->n, k.C, k.H, k.K, b->rl_n, warm, do_lb, c->no_stage, L.px_G, corr ? c->tr_n : 0);
   const int lpm = V.lpm;
   L.nslots = V.nslots;
   L.G = V.G;
@@ -400,6 +416,28 @@ static int ctl_prepare(llampc_ctl* c, const double* x_t, llampc_ctl::Prep& P) {
     }
   }
   lds = std::max<size_t>(lds, 82 * 1024); // one block per CU, as the plan launch (sc1 hand-offs)
+  P.corr = corr;
+  if (corr) {
+    // the path state and the read-back by tick parity (ctl.hpp CtlCorridor): tick t reads what tick
+    // t - 1 wrote and writes its own copy
+    CtlCorridor& q = P.cor;
+    const double* tr = c->d_track.get();
+    const size_t tn = (size_t)c->tr_n, ps = 2 * (size_t)kCtlPathStride;
+    const int wr = (int)(t & 1), rd = wr ^ 1;
+    q = CtlCorridor{};
+    q.trk = TrackK{tr, tr + tn, tr + 2 * tn, c->tr_n, 0, c->tr_L};
+    q.hw = c->tr_width / 2 - c->cor_margin;
+    q.weight = c->cor_w;
+    q.hp_tag = c->d_hp_tag.get();
+    q.path_rd = c->d_cor.get() + rd * ps;
+    q.path_wr = c->d_cor.get() + wr * ps;
+    q.valid_rd = c->d_cor_flag.get() + rd;
+    q.valid_wr = c->d_cor_flag.get() + wr;
+    q.dbg = c->d_cor.get() + 2 * ps + (size_t)wr * kCtlCorDbgDoubles;
+    q.dbg_valid = c->d_cor_flag.get() + 2 + wr;
+    q.path_ok = c->cor_prev ? 1 : 0;
+    q.dbg_cost = c->d_cor_cost.get();
+  }
   P.L = L;
   P.lpm = lpm;
   P.lds = lds;
@@ -412,9 +450,16 @@ static int ctl_prepare(llampc_ctl* c, const double* x_t, llampc_ctl::Prep& P) {
   return LLAMPC_OK;
 }
 
+// A prepared tick's one launch: the corridor kernel for a corridor tick.
+static hipError_t ctl_launch(const llampc_ctl::Prep& P, hipStream_t s) {
+  return P.corr ? launch_ctl_corr(P.L, P.cor, P.lpm, P.lds, s) : launch_ctl(P.L, P.lpm, P.lds, s);
+}
+
 // The host state after tick P.t was enqueued (or its armed launch fired).
 static void ctl_commit(llampc_ctl* c, const llampc_ctl::Prep& P) {
   llampc_bank* b = c->b;
+  c->cor_prev = P.corr;
+  c->cor_nslots = P.corr ? P.L.nslots : 0;
   c->hseq = P.hs;
   c->seq = P.seq;
   if (P.L.px_G) {                        // committed after the launch was enqueued (next_seq)
@@ -445,7 +490,7 @@ static int ctl_arm(llampc_ctl* c) {
   llampc_ctl::Prep P;
   int rc;
   if ((rc = ctl_refresh(c, false)) || (rc = ctl_prepare(c, nullptr, P))) return rc;
-  HIP_TRY(launch_ctl(P.L, P.lpm, P.lds, c->b->stream));
+  HIP_TRY(ctl_launch(P, c->b->stream));
   c->arm = P;
   c->armed = true;
   c->arm_t = std::chrono::steady_clock::now();
@@ -525,7 +570,7 @@ int llampc_ctl_tick_async(llampc_ctl* c, const double* x_t) {
   }
   {
     TimedLaunch tl(b, 0, b->stream);
-    HIP_TRY(launch_ctl(P.L, P.lpm, P.lds, b->stream));
+    HIP_TRY(ctl_launch(P, b->stream));
   }
   ctl_commit(c, P);
   ctl_arm_later(c);
@@ -696,6 +741,7 @@ static int ctl_check_global(const llampc_bank* b, int64_t n_global) {
 static int ctl_upload_global(llampc_ctl* c, const char* other, const double* gparams, int64_t n_global,
                              DevBuf<double>& gp) {
   if (c->pending) return fail(LLAMPC_E_STATE, "a controller tick is outstanding");
+  if (c->cor_w > 0) return fail(LLAMPC_E_STATE, "a corridor controller is unsharded (llampc_ctl_set_corridor)");
   if (c->t != 0) return fail(LLAMPC_E_STATE, "set the exchange before the first tick");
   if (other) return fail(LLAMPC_E_STATE, "the controller already exchanges over %s", other);
   ctl_cancel(c);                         // no armed launches with an exchange
@@ -846,6 +892,124 @@ int llampc_ctl_merge(const double* vals, const int64_t* gids, int32_t G, int32_t
                      i = gids[g * (K + 1) + K];
                    },
                    G, nan_policy == LLAMPC_NAN_FIRST, *best_val, *best);
+  return LLAMPC_OK;
+}
+
+int llampc_ctl_set_track(llampc_ctl* c, const double* centre, const double* theta, int32_t n, double track_length,
+                         double track_width) {
+  if (!c || !centre || !theta) return fail(LLAMPC_E_ARG, "NULL argument");
+  char why[128];
+  if (track_tables_invalid(centre, theta, n, track_length, track_width, why, sizeof why)) return fail(LLAMPC_E_ARG, "%s", why);
+  std::lock_guard<std::mutex> lc(c->mu);
+  if (c->pending) return fail(LLAMPC_E_STATE, "a controller tick is outstanding");
+  if (c->cor_w > 0) return fail(LLAMPC_E_STATE, "switch the corridor off before replacing its track");
+  llampc_bank* b = c->b;
+  std::lock_guard<std::mutex> lk(b->mu);
+  bank_disarm(b);
+  DeviceGuard g(b->device);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // no launch reads the tables being replaced
+  c->tr_n = 0;
+  if (int rc = c->d_track.reserve(3 * (size_t)n, 0, "track tables")) return rc;
+  std::vector<double> h(3 * (size_t)n);
+  std::memcpy(h.data(), centre, 2 * (size_t)n * sizeof(double));
+  std::memcpy(h.data() + 2 * (size_t)n, theta, (size_t)n * sizeof(double));
+  HIP_TRY(hipMemcpy(c->d_track.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  c->tr_n = n;
+  c->tr_L = track_length;
+  c->tr_width = track_width;
+  return LLAMPC_OK;
+}
+
+int llampc_ctl_set_corridor(llampc_ctl* c, double weight, double margin) {
+  if (!c) return fail(LLAMPC_E_ARG, "controller is NULL");
+  std::lock_guard<std::mutex> lc(c->mu);
+  ctl_cancel(c);                         // as every other call: the tick after launches normally
+  if (c->pending) return fail(LLAMPC_E_STATE, "a controller tick is outstanding");
+  if (!c->tr_n) return fail(LLAMPC_E_STATE, "no track set: call llampc_ctl_set_track first");
+  if (c->mb || c->xg_world) return fail(LLAMPC_E_STATE, "a sharded controller has no corridor ticks");
+  if (!(weight >= 0) || !std::isfinite(weight)) return fail(LLAMPC_E_ARG, "weight must be finite and >= 0");
+  if (!std::isfinite(margin) || !(c->tr_width / 2 - margin > 0))
+    return fail(LLAMPC_E_ARG, "margin %g leaves no corridor (track width %g)", margin, c->tr_width);
+  if (weight > 0) {
+    llampc_bank* b = c->b;
+    const llampc_ctl_cfg& k = c->cfg;
+    const CtlShape V = ctl_shape(b->n, k.C, k.H, k.K, b->rl_n, false, true, c->no_stage, 0, c->tr_n);
+    if (V.lds > kCtlLdsMax) return fail(LLAMPC_E_ARG, "a corridor tick needs %zu B of LDS (> 160 KiB)", V.lds);
+    if (!c->d_cor) {
+      DeviceGuard g(b->device);
+      DevBuf<double> cor;
+      DevBuf<uint64_t> tag;
+      DevBuf<int32_t> flag;
+      int rc;
+      if ((rc = cor.zalloc(4 * (size_t)kCtlPathStride + 2 * (size_t)kCtlCorDbgDoubles, "corridor path state")) ||
+          (rc = tag.zalloc(12 * (size_t)LLAMPC_HMAX, "corridor words")) || (rc = flag.zalloc(4, "corridor flags")))
+        return rc;
+      c->d_cor = std::move(cor);
+      c->d_hp_tag = std::move(tag);
+      c->d_cor_flag = std::move(flag);
+    }
+    if (k.debug_inputs && !c->d_cor_cost) {
+      DeviceGuard g(b->device);
+      if (int rc = c->d_cor_cost.zalloc((size_t)kCtlSlotsMax * k.C, "corridor costs")) return rc;
+    }
+  } else {
+    c->cor_prev = false;                 // off: the path state is invalid from here on
+  }
+  c->cor_w = weight;
+  c->cor_margin = margin;
+  return LLAMPC_OK;
+}
+
+int llampc_ctl_corridor(llampc_ctl* c, double* path, double* hp, double* theta, int32_t* valid) {
+  if (!c || !path || !hp || !theta || !valid) return fail(LLAMPC_E_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lc(c->mu);
+  if (c->pending) return fail(LLAMPC_E_STATE, "a controller tick is outstanding");
+  if (!c->d_cor || !c->cor_prev) return fail(LLAMPC_E_STATE, "the last tick was not a corridor tick");
+  DeviceGuard g(c->b->device);
+  ctl_cancel(c);                         // an armed launch would hold the stream (re-armed next tick)
+  HIP_TRY(hipStreamSynchronize(c->b->stream));
+  const int H = c->cfg.H;
+  const int cp = (int)((c->t - 1) & 1);  // the last tick's copy
+  std::vector<double> h(kCtlCorDbgDoubles);
+  int32_t v = 0;
+  HIP_TRY(hipMemcpy(h.data(), c->d_cor.get() + 4 * (size_t)kCtlPathStride + (size_t)cp * kCtlCorDbgDoubles,
+                    h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&v, c->d_cor_flag.get() + 2 + cp, sizeof v, hipMemcpyDeviceToHost));
+  for (int r = 0; r < 2; ++r) std::memcpy(path + (size_t)r * (H + 1), h.data() + (size_t)r * kCtlPathStride, (H + 1) * sizeof(double));
+  std::memcpy(hp, h.data() + 2 * kCtlPathStride, 6 * (size_t)H * sizeof(double));
+  std::memcpy(theta, h.data() + 2 * kCtlPathStride + 6 * LLAMPC_HMAX, (size_t)H * sizeof(double));
+  *valid = v;
+  return LLAMPC_OK;
+}
+
+int llampc_ctl_corridor_costs(llampc_ctl* c, double* costs, int32_t* nslots) {
+  if (!c || !costs || !nslots) return fail(LLAMPC_E_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lc(c->mu);
+  if (c->pending) return fail(LLAMPC_E_STATE, "a controller tick is outstanding");
+  if (!c->d_cor_cost) return fail(LLAMPC_E_STATE, "controller created without debug_inputs");
+  if (!c->cor_prev) return fail(LLAMPC_E_STATE, "the last tick was not a corridor tick");
+  DeviceGuard g(c->b->device);
+  ctl_cancel(c);                         // an armed launch would hold the stream (re-armed next tick)
+  HIP_TRY(hipStreamSynchronize(c->b->stream));
+  HIP_TRY(hipMemcpy(costs, c->d_cor_cost.get(), (size_t)c->cor_nslots * c->cfg.C * sizeof(double), hipMemcpyDeviceToHost));
+  *nslots = c->cor_nslots;
+  return LLAMPC_OK;
+}
+
+// llampc_ctl_variant's fields for a corridor tick on a centre line of track_n points, then the
+// corridor block count: from the same ctl_shape.
+int llampc_ctl_variant_corridor(int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl_n, int32_t track_n,
+                                int32_t out[10]) {
+  if (!out) return fail(LLAMPC_E_ARG, "NULL argument");
+  constexpr int32_t kCtlVariantCMax = 1 << 16;
+  if (n < 1 || C < 1 || C > kCtlVariantCMax || H < 1 || H > LLAMPC_HMAX || K < 1 || K > LLAMPC_KMAX || rl_n < 2 ||
+      track_n < 2 || track_n > kTrackMaxPoints)
+    return fail(LLAMPC_E_ARG, "n=%lld C=%d (1..%d) H=%d (1..%d) K=%d (1..%d) rl_n=%d track_n=%d (2..%d)", (long long)n, C,
+                kCtlVariantCMax, H, LLAMPC_HMAX, K, LLAMPC_KMAX, rl_n, track_n, kTrackMaxPoints);
+  const CtlShape V = ctl_shape(n, C, H, K, rl_n, false, true, false, 0, track_n);
+  if (V.lds > kCtlLdsMax) return fail(LLAMPC_E_ARG, "a corridor tick needs %zu B of LDS (> 160 KiB)", V.lds);
+  const int32_t v[10] = {V.lpm, V.G, V.cpl, V.mpb, V.s4, V.zfit, V.R, V.nb_lb, V.nb_la, V.nb_cor};
+  std::memcpy(out, v, sizeof v);
   return LLAMPC_OK;
 }
 

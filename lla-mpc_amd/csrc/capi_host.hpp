@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -63,6 +64,26 @@ inline CostK make_cost(const llampc_cost& c, double Ts) {
   k.enforce = c.enforce_bounds;
   k.pad = 0;
   return k;
+}
+
+// A track's centre line as llampc_nlp_set_track and llampc_ctl_set_track accept it: finite points
+// centre [2][n], arc lengths theta [n] from 0 strictly increasing, a closed length beyond the last and
+// long enough for the tangent's two points, a positive width.  Null if valid, else what is wrong (in buf).
+inline const char* track_tables_invalid(const double* centre, const double* theta, int32_t n, double track_length,
+                                        double track_width, char* buf, size_t nbuf) {
+  if (n < 2 || n > kTrackMaxPoints) return (std::snprintf(buf, nbuf, "n=%d outside [2, %d]", n, kTrackMaxPoints), buf);
+  for (int64_t i = 0; i < 2 * (int64_t)n; ++i)
+    if (!std::isfinite(centre[i])) return (std::snprintf(buf, nbuf, "centre line: entry %lld is not finite", (long long)i), buf);
+  if (!std::isfinite(track_length) || !std::isfinite(track_width)) return (std::snprintf(buf, nbuf, "length / width not finite"), buf);
+  if (theta[0] != 0.0) return (std::snprintf(buf, nbuf, "theta[0] must be 0"), buf);
+  for (int32_t i = 1; i < n; ++i)
+    if (!std::isfinite(theta[i]) || !(theta[i] > theta[i - 1]))
+      return (std::snprintf(buf, nbuf, "theta must be finite and strictly increasing (entry %d)", i), buf);
+  if (!(track_length > theta[n - 1])) return (std::snprintf(buf, nbuf, "track_length must exceed theta[n-1]"), buf);
+  // the tangent's points lie 2 kTangentEps apart: a shorter lap would meet itself
+  if (!(track_length > 4 * kTangentEps)) return (std::snprintf(buf, nbuf, "track_length must exceed %g", 4 * kTangentEps), buf);
+  if (!(track_width > 0)) return (std::snprintf(buf, nbuf, "track_width must be > 0"), buf);
+  return nullptr;
 }
 
 // A corridor hp [H][6] (llampc_nlp_solve_corridor: per step (a0, a1, b, c0, c1, d), a.p <= b and
@@ -339,10 +360,14 @@ inline void bank_final(const BankView& b, FinalLaunch& f) {
 struct CtlShape {
   int lpm, G, cpl, mpb, s4, zfit, R, nb_lb, nb_la, nslots;
   size_t lds, poll_off;
+  int nb_cor;                            // corridor blocks, between the look-back's and the look-ahead's
 };
 constexpr size_t kCtlLdsMax = 160 * 1024;
+// cor_n > 0: a corridor tick (ctl_corr.hip ctl_kernel_corr) on a centre line of cor_n points — never
+// staged (the corridor rollout is unstaged and unsplit), H corridor blocks, and the LDS the largest
+// of the roles': the look-ahead layout with the half-planes behind it, a corridor block's tables.
 inline CtlShape ctl_shape(int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl_n, bool warm, bool do_lb,
-                          bool no_stage, int px_G) {
+                          bool no_stage, int px_G, int32_t cor_n = 0) {
   CtlShape s{};
   s.R = lookback_r(n, K);
   s.nb_lb = do_lb ? lookback_blocks_r(n, s.R) : 1;
@@ -353,6 +378,12 @@ inline CtlShape ctl_shape(int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl
   s.mpb = kBlock / (s.G * s.lpm);
   s.nb_la = (s.nslots + s.mpb - 1) / s.mpb;
   s.zfit = ctl_zfit(C, H) ? 1 : 0;
+  if (cor_n > 0) {
+    s.nb_cor = H;
+    s.lds = ctl_lds_bytes(H, C, rl_n, s.nb_lb, K, &s.poll_off, false, px_G, 0, ctl_corr_extra(H),
+                          ctl_corridor_block_lds(cor_n));
+    return s;
+  }
   // the look-ahead blocks stage every (candidate, step)'s input terms when they fit in LDS
   // (CtlLaunch.s4; LLAMPC_CTL_NO_STAGE=1 at create: never, for A/B runs)
   size_t poll_s4 = 0;

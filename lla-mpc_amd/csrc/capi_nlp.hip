@@ -101,18 +101,8 @@ int llampc_nlp_create(llampc_bank* b, const llampc_nlp_cfg* cfg, llampc_nlp** ou
 int llampc_nlp_set_track(llampc_nlp* p, const double* centre, const double* theta, int32_t n, double track_length,
                          double track_width) {
   if (!p || !centre || !theta) return fail(LLAMPC_E_ARG, "NULL argument");
-  if (n < 2 || n > kTrackMaxPoints) return fail(LLAMPC_E_ARG, "n=%d outside [2, %d]", n, kTrackMaxPoints);
-  for (int64_t i = 0; i < 2 * (int64_t)n; ++i)
-    if (!std::isfinite(centre[i])) return fail(LLAMPC_E_ARG, "centre line: entry %lld is not finite", (long long)i);
-  if (!std::isfinite(track_length) || !std::isfinite(track_width)) return fail(LLAMPC_E_ARG, "length / width not finite");
-  if (theta[0] != 0.0) return fail(LLAMPC_E_ARG, "theta[0] must be 0");
-  for (int32_t i = 1; i < n; ++i)
-    if (!std::isfinite(theta[i]) || !(theta[i] > theta[i - 1]))
-      return fail(LLAMPC_E_ARG, "theta must be finite and strictly increasing (entry %d)", i);
-  if (!(track_length > theta[n - 1])) return fail(LLAMPC_E_ARG, "track_length must exceed theta[n-1]");
-  // the tangent's points lie 2 kTangentEps apart: a shorter lap would meet itself
-  if (!(track_length > 4 * kTangentEps)) return fail(LLAMPC_E_ARG, "track_length must exceed %g", 4 * kTangentEps);
-  if (!(track_width > 0)) return fail(LLAMPC_E_ARG, "track_width must be > 0");
+  char why[128];
+  if (track_tables_invalid(centre, theta, n, track_length, track_width, why, sizeof why)) return fail(LLAMPC_E_ARG, "%s", why);
   std::lock_guard<std::mutex> lp(p->mu);
   llampc_bank* b = p->b;
   std::lock_guard<std::mutex> lk(b->mu);

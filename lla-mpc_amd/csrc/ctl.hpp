@@ -410,4 +410,56 @@ hipError_t launch_constant_speed(const CsLaunch& a, hipStream_t s);
 
 hipError_t launch_ctl(const CtlLaunch& c, int lpm, size_t lds, hipStream_t s);
 
+// ---- the corridor tick (llampc_ctl_set_corridor; ctl_corr.hip ctl_kernel_corr) ---------------------
+// The soft track corridor of the look-ahead (rollout_dev.hpp kRCorr) inside the controller tick:
+// ctl_kernel_corr's own trailing argument, as PlanCorridor is plan_kernel_corr's, so CtlLaunch keeps
+// its layout.  The corridor hp_t [H][6] of tick t runs along the PREVIOUS tick's chosen rollout
+// shifted one step (constraints.default_path's prev_xmpc rule): known before x_t, so the H corridor
+// blocks (blocks [nb_lb, nb_lb + H)) build it without waiting for anything.
+//   path state   X_0..X_H, the positions of a tick's chosen rollout (the selection slot's best
+//                candidate; X_0 = x_t) as [2][HMAX + 1], with a valid flag: the chosen cost and all
+//                positions finite.  Two copies by tick parity: tick t's corridor blocks read copy
+//                (t - 1) & 1 while its selection slot's block writes copy t & 1, so a corridor block
+//                that starts late in the launch never reads a half-written path.
+//   path_ok      the host's half of the validity rule: tick t - 1 of this controller was a corridor
+//                tick.  Invalid: every row is constraints.disabled's (0, 0, +inf, 0, 0, +inf).
+//   hp_tag       [12 H] tagged words, the halves of row k - 1's six values (hi, lo) at 12 (k - 1) on:
+//                corridor block k publishes them, every look-ahead block polls all of them.
+//   dbg          what llampc_ctl_corridor reads back, by tick parity too (an armed launch's corridor
+//                blocks run before the read-back of the tick before): per copy P [2][HMAX + 1] |
+//                hp [HMAX][6] | theta [HMAX], and the path's validity in dbg_valid.
+constexpr int kCtlPathStride = LLAMPC_HMAX + 1;
+constexpr int kCtlCorDbgDoubles = 2 * kCtlPathStride + 7 * LLAMPC_HMAX;
+struct CtlCorridor {
+  TrackK trk;
+  double hw, weight;          // track_width / 2 - margin; w > 0
+  uint64_t* hp_tag;
+  const double* path_rd;      // tick t - 1's X [2][HMAX + 1]
+  double* path_wr;            // tick t's
+  const int32_t* valid_rd;
+  int32_t* valid_wr;
+  double* dbg;                // this tick's copy
+  int32_t* dbg_valid;
+  int32_t path_ok;
+  int32_t pad;
+  double* dbg_cost;           // null, or every rolled-out cost of this tick [nslots][C] (cfg.debug_inputs;
+                              //   llampc_ctl_corridor_costs): written after the doorbell, one copy
+};
+// The path rule (constraints.default_path with prev_xmpc): P_j = X_{j+1} for j < H, P_H = X_H —
+// the index of X that path point j reads.
+__host__ __device__ constexpr int ctl_path_index(int j, int H) { return j + 1 < H ? j + 1 : H; }
+// Whether a chosen rollout may serve as the next tick's path: a finite cost, finite positions
+// (X, Y: H + 1 values each).
+__host__ __device__ inline bool ctl_path_valid(double cost, const double* X, const double* Y, int H) {
+  bool ok = fabs(cost) <= __DBL_MAX__;
+  for (int j = 0; j <= H; ++j) ok = ok && fabs(X[j]) <= __DBL_MAX__ && fabs(Y[j]) <= __DBL_MAX__;
+  return ok;
+}
+// LDS a corridor tick's look-ahead block keeps after its layout (ctl_lds_bytes' `extra`): hp [H][6],
+// then the winner's positions [2][H + 1] and its flag; and a corridor block's whole request
+// (corridor_block_dev.hpp: two reduction rows, then the centre line's three tables).
+__host__ __device__ constexpr size_t ctl_corr_extra(int H) { return 48 * (size_t)H + 16 * (size_t)(H + 1) + 16; }
+__host__ __device__ constexpr size_t ctl_corridor_block_lds(int n) { return 64 + 24 * (size_t)n; }
+hipError_t launch_ctl_corr(const CtlLaunch& c, const CtlCorridor& cor, int lpm, size_t lds, hipStream_t s);
+
 }  // namespace llampc

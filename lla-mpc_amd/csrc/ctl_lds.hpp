@@ -67,9 +67,13 @@ constexpr size_t kCtlPollBytes = 4096;   // ctl_complete's area (layout there)
 
 // LDS bytes of the controller launch and the completing block's area offset; s4: with the staged
 // input terms (CtlLaunch.s4).
+// extra: bytes a look-ahead block keeps after its layout, from L.end on (a corridor tick's half-planes
+// and winner positions, ctl.hpp ctl_corr_extra); role_min: another block role's whole request (the
+// corridor blocks' track tables).
 inline size_t ctl_lds_bytes(int H, int C, int n, int nb_lb, int K, size_t* poll_off, bool s4 = false, int px_G = 0,
-                            int n_spec = 0) {
-  const CtlLds L = ctl_lds(H, C, n, s4);
+                            int n_spec = 0, size_t extra = 0, size_t role_min = 0) {
+  CtlLds L = ctl_lds(H, C, n, s4);
+  L.end = std::max(align16(L.end + extra), role_min);
   const size_t Lb = nb_lb;
   const size_t lbf = lb_final_lds_bytes(nb_lb, K);                      // lb_final's region, the wave lists
   const size_t px = px_G ? kScratchBytes + ctl_px_bytes(px_G, K) : 0;   // ctl_exchange's region

@@ -1,6 +1,7 @@
 // ctl_lookahead_dev.hpp — a look-ahead block of the controller tick (blocks [nb_lb, nb_lb +
 // nb_la)): the tick's reference (cs_dev.hpp) and candidates (ctl_cand_dev.hpp), the wait for
-// the selection, its slots' rollouts and each slot's best candidate published.  Included by ctl.hip only.
+// the selection, its slots' rollouts and each slot's best candidate published.  Included by ctl.hip and
+// ctl_corr.hip (the corridor tick: CORR).
 #pragma once
 #include "cs_dev.hpp"
 #include "ctl_cand_dev.hpp"
@@ -24,8 +25,13 @@ __device__ __forceinline__ void ctl_group_sync(int* arrived, int target) {
   }
 }
 
-template <int LPM>
-__device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsigned char* smem, const Scratch& sc) {
+// CORR (ctl_corr.hip, a corridor tick: c.s4 = 0, c.n_spec = 0): next to the wait for the selection the
+// block polls the tick's half-planes (cor->hp_tag, published by the corridor blocks, which have lower
+// indices and wait for nothing) into LDS, rolls out unsplit with the corridor term, and the selection
+// slot's block re-runs its winner with the positions stored: the next tick's path (ctl.hpp CtlCorridor).
+template <int LPM, bool CORR = false>
+__device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsigned char* smem, const Scratch& sc,
+                                              const CtlCorridor* cor = nullptr) {
   const int tid = threadIdx.x;
   const int H = c.la.H, C = c.la.C;
   const RacelineK rl = c.la.rl;
@@ -41,10 +47,24 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
   int* arrived = reinterpret_cast<int*>(smem + L.misc + 688);              // waves 1-3 (ctl_group_sync)
   double* s4 = reinterpret_cast<double*>(smem + L.s4);                      // s4: the staged inputs
   int* door_res = reinterpret_cast<int*>(smem + L.misc + 720);
+  // CORR only, after the layout (ctl.hpp ctl_corr_extra): hp [H][6] | the winner's X | Y [2][H + 1] |
+  // its cost is finite; and in misc whether a half-plane word never came
+  struct CorLds {
+    double *hp, *pos;
+    int *flag, *late;
+  };
+  auto cor_lds = [&] {
+    double* hp = reinterpret_cast<double*>(smem + L.end);
+    return CorLds{hp, hp + 6 * H, reinterpret_cast<int*>(hp + 6 * H + 2 * (H + 1)),
+                  reinterpret_cast<int*>(smem + L.misc + 724)};
+  };
   CTL_STAMP(blockIdx.x, 0);
   const bool armed = c.door != nullptr;
   if (!armed && tid < 6) x0[tid] = ctl_xt(c, tid);
   if (tid == 0) *arrived = 0;
+  if constexpr (CORR) {
+    if (tid == 0) *cor_lds().late = 0;
+  }
   const CtlState* st = c.st;
   const double* prev_seq = st->has_seq ? &st->useq[0][0] : nullptr;
   // rt.py:278-282: projidx and the mu bracket (mu-hat or the fixed mu) come from the host's
@@ -170,6 +190,19 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
     slot_id[tid] = id;
     sel_late[tid] = late;
   }
+  if constexpr (CORR) {
+    // the tick's half-planes: each thread polls its share of the 12 H tagged halves (word 2 i the
+    // high half of value i, 2 i + 1 the low one) under the launch's bound; a word that never comes
+    // leaves a zero and the slots' late bit (the record then reads LLAMPC_STATUS_POLL_TIMEOUT)
+    const CorLds cl = cor_lds();
+    uint32_t* hp32 = reinterpret_cast<uint32_t*>(cl.hp);
+    for (int e = tid; e < 12 * H; e += kBlock) {
+      int late = 0;
+      const uint32_t v = poll_tag(cor->hp_tag, e, c.seq, c.poll, late);
+      hp32[(e & ~1) | ((e & 1) ^ 1)] = late ? 0u : v;
+      if (late) *cl.late = 1;
+    }
+  }
   __syncthreads();
   if (c.n_spec) {                       // launch-uniform: a slot whose model a spec block rolls out: bit 1
     if (tid < 64) {
@@ -260,7 +293,10 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
       if (cc >= C) break;
       bool bad = false;
       double J;
-      if (c.s4) {                       // block-uniform: the staged input terms
+      if constexpr (CORR) {             // unsplit, unstaged, the corridor term (rollout_dev.hpp kRCorr)
+        J = rollout<0, LPM, kRF | kRFast | kRCorr | kRPos>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, bad,
+                                                          nullptr, nullptr, nullptr, 0, nullptr, cor_lds().hp, cor->weight);
+      } else if (c.s4) {                // block-uniform: the staged input terms
         if (kSplit && diagQP)
           J = rollout<0, LPM, kRF | kRFast | kRS4 | kRSplitQ>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, bad,
                                                               nullptr, s4);
@@ -274,13 +310,29 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
       merge_bad<LPM>(bad);
       if (__builtin_expect(__any(bad), 0)) {
         bool unused = false;
-        if (bad)
+        if constexpr (CORR) {
+          if (bad)
+            J = rollout<0, LPM, kRF | kRCorr | kRPos>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, unused,
+                                                     nullptr, nullptr, nullptr, 0, nullptr, cor_lds().hp, cor->weight);
+        } else if (bad) {
           J = rollout<0, LPM, kRF>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, unused);
+        }
       }
       if (sub == 0) nf += !isfinite(J);
+      if constexpr (CORR) {             // tests: every rolled-out cost, not the slot's best alone
+        if (cor->dbg_cost != nullptr && sub == 0) cor->dbg_cost[(size_t)slot * C + cc] = J;
+      }
       if (less_nan_last(J, cc, bv, bc)) {
         bv = J;
         bc = cc;
+      }
+    }
+  }
+  if constexpr (CORR) {                 // a slot of the tick that rolls nothing out (no such model): NaN
+    if (cor->dbg_cost != nullptr && !live && sub == 0 && si < mpb && slot < c.nslots) {
+      for (int j = 0; j < cpl; ++j) {
+        const int cc = g + j * G;
+        if (cc < C) cor->dbg_cost[(size_t)slot * C + cc] = __builtin_nan("");
       }
     }
   }
@@ -318,10 +370,68 @@ __device__ __forceinline__ void ctl_lookahead(const CtlLaunch& c, int blk, unsig
   }
   // (h) publish: cost (hi, lo), candidate, non-finite count | late << 31 (tagged words)
   if (g == 0 && sub == 0 && si < mpb && slot < c.nslots && !spec_hit) {
-    const uint32_t nfw = (uint32_t)nf | ((uint32_t)(sel_late[si] & 1) << 31);
+    uint32_t nfw = (uint32_t)nf | ((uint32_t)(sel_late[si] & 1) << 31);
+    if constexpr (CORR) nfw |= (uint32_t)(*cor_lds().late != 0) << 31;
     publish_slot(c.slot_tag + 4 * (size_t)slot, c.seq, bv, bc, nfw);
   }
   CTL_STAMP(blockIdx.x, 5);
+  if constexpr (CORR) {
+    // (i) the path state for the next tick, off the tick's critical path (the slot is published): the
+    //     block that holds the selection's slot re-runs its winner — the instantiations and operands
+    //     of the published cost, so the same roundings — with the positions stored, and wave 0 copies
+    //     them out with the validity flag (ctl.hpp ctl_path_valid)
+    const int ss = c.warm ? 0 : c.K;
+    const CorLds cl = cor_lds();
+    double* ppos = cl.pos;
+    int* pflag = cl.flag;
+    if (blk == ss / mpb) {              // block-uniform
+      const int t0 = (ss - blk * mpb) * G * LPM;
+      if (tid >= t0 && tid < t0 + LPM) {
+        double Jw = __builtin_nan("");
+        double* dp = sub == 0 ? ppos : nullptr;
+        if (live && bc >= 0 && bc < C) {
+          const int cc = (int)bc;
+          StageK sk = make_stage<LPM>(veh, t, sub, Ts, Ts * veh.inv_mass);
+          constexpr bool kScaled = scaled_yaw(LPM);
+          if (kScaled) sk.ch[0].lw = sk.ch[0].lw / Ts;
+          if (kScaled && LPM == 1) sk.ch[1].lw = sk.ch[1].lw / Ts;
+          if (kScaled && LPM == 4 && sub >= 2) {
+            sk.ch[0].lw = 0.0;
+            sk.ch[0].sg = 0.0;
+            sk.ch[0].B = 0.0;
+            sk.ch[0].nsB = 0.0;
+            sk.Bfw = 0.0;
+          }
+          const FusedK fq = make_fused(veh, sk, Ts, kScaled, LPM == 4);
+          const fm::FmK K = load_la_consts<0, LPM>();
+          bool bad = false, unused = false;
+          Jw = rollout<0, LPM, kRF | kRFast | kRCorr | kRPos>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, bad,
+                                                             nullptr, nullptr, dp, H + 1, nullptr, cl.hp, cor->weight);
+          merge_bad<LPM>(bad);
+          if (bad)
+            Jw = rollout<0, LPM, kRF | kRCorr | kRPos>(c.la, cc, 0, x0, sx, Ul, veh, t, sk, q, Ts, up0, up1, K, fq, unused,
+                                                      nullptr, nullptr, dp, H + 1, nullptr, cl.hp, cor->weight);
+        }
+        if (sub == 0) {
+          ppos[0] = x0[0];
+          ppos[H + 1] = x0[1];
+          *pflag = (int)(fabs(Jw) <= __DBL_MAX__);
+        }
+      }
+      __syncthreads();
+      if (tid < 64) {
+        bool ok = *pflag != 0;
+        for (int e = tid; e < 2 * (H + 1); e += 64) {
+          const int row = e / (H + 1), j = e - row * (H + 1);
+          const double v = ppos[e];
+          ok = ok && fabs(v) <= __DBL_MAX__;
+          cor->path_wr[row * kCtlPathStride + j] = v;
+        }
+        const int all = __all(ok);
+        if (tid == 0) *cor->valid_wr = all;
+      }
+    }
+  }
 }
 
 }  // namespace llampc

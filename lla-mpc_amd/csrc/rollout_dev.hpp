@@ -89,6 +89,9 @@ enum RolloutFlag : unsigned {
   kRQuadr = 1u << 9,  // QUADR (with SPLIT; the plan kernel's lookahead_block): the component is a per-step quadrature in
                       //   quad lanes 2 / 3 (dyn.hpp step_fused kPosQuadr), no position broadcast in the stages; lanes 0 / 1
                       //   hold garbage in x[0] and track, J = (J_X + J_Y) + act from lanes 2 and 3
+  kRPos = 1u << 10,   // POS (the controller tick's corridor look-ahead, with CORR): where `dpos` is not null, the position
+                      //   after step k to dpos[k + 1] (X) and dpos[dstride + k + 1] (Y) — the same evaluation with or
+                      //   without the stores, so a winner's re-run returns the published cost's own positions
 };
 // What DEFER returns in *dout: the reference is not known yet, so the lane stores its position
 // component after step k at dpos[k dstride] instead of accumulating the tracking term, and
@@ -202,6 +205,13 @@ __device__ __forceinline__ double rollout(const LookaheadLaunch& a, int c, int64
     else if (FAST) step_fast<INTEG, LPM>(veh, t, sk, x, u, Ts, K, dm);
     else step<INTEG>(veh, t, x, u, Ts);
     if constexpr (CORR) pen = pen + corridor_slack2(hp + 6 * k, x[0], x[1]);
+    if constexpr ((F & kRPos) != 0) {
+      static_assert(CORR, "position output: the corridor rollout (both components in the lane, unscaled)");
+      if (dpos != nullptr) {
+        dpos[k + 1] = x[0];
+        dpos[dstride + k + 1] = x[1];
+      }
+    }
     if (DEFER) {                        // the position component, for defer_cost
       dpos[k * dstride] = x[0];
     } else if (SPLIT) {                 // this lane's component of the reference and term

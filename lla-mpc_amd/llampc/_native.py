@@ -170,6 +170,15 @@ _SIGNATURES = {
     "llampc_ctl_set_gather": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _dp, C.c_int64]),
     "llampc_ctl_record_words": (C.c_int32, [C.c_int32]),
     "llampc_ctl_variant": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    # centre [2][n], theta [n], n, track_length, track_width
+    "llampc_ctl_set_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double]),
+    "llampc_ctl_set_corridor": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    # -> path [2][H+1], hp [H][6], theta [H], valid
+    "llampc_ctl_corridor": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    # -> costs [nslots][C], nslots
+    "llampc_ctl_corridor_costs": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_int32)]),
+    "llampc_ctl_variant_corridor": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_int32)]),
     "llampc_ctl_shard_record": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "llampc_ctl_resume": (C.c_int, [C.c_void_p, C.c_void_p]),
     "llampc_ctl_set_prelaunch": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -288,6 +297,14 @@ def ctl_variant(n: int, C_: int, H: int, K: int, rl_n: int) -> dict:
     out = (C.c_int32 * 9)()
     check(load().llampc_ctl_variant(int(n), int(C_), int(H), int(K), int(rl_n), out))
     return dict(zip(CTL_VARIANT_FIELDS, (int(v) for v in out)))
+
+
+def ctl_variant_corridor(n: int, C_: int, H: int, K: int, rl_n: int, track_n: int) -> dict:
+    """The launch shape of a corridor tick (llampc_ctl_variant_corridor; host only) on a centre line of
+    track_n points: ctl_variant's fields (s4 = 0), then nb_cor, the corridor blocks."""
+    out = (C.c_int32 * 10)()
+    check(load().llampc_ctl_variant_corridor(int(n), int(C_), int(H), int(K), int(rl_n), int(track_n), out))
+    return dict(zip(CTL_VARIANT_FIELDS + ("nb_cor",), (int(v) for v in out)))
 
 
 def dptr(a: np.ndarray | None):

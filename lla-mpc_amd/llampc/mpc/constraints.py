@@ -27,6 +27,34 @@ import numpy as np
 TANGENT_EPS = 0.05
 
 
+def require_track(track, what):
+    """The track attributes a device-built corridor reads (``setupNLP(device_corridor=True)``,
+    ``LLAMPC(corridor_weight=...)``): raises ValueError naming the missing ones."""
+    missing = [k for k in ("center_line", "theta_track", "track_length", "track_width")
+               if getattr(track, k, None) is None]
+    if track is None or missing:
+        raise ValueError(f"{what} needs a track with center_line, theta_track, track_length "
+                         f"and track_width (missing: {'the track' if track is None else ', '.join(missing)})")
+
+
+def require_margin(track, margin):
+    """A margin that leaves a corridor on the track (a NaN margin does not)."""
+    if not float(margin) < float(track.track_width) / 2:
+        raise ValueError(f"corridor_margin {margin} leaves no corridor "
+                         f"(track width {track.track_width})")
+
+
+def track_tables(track):
+    """(centre [2, n], theta [n], track_length, track_width) as llampc_nlp_set_track and
+    llampc_ctl_set_track take them."""
+    centre = np.ascontiguousarray(track.center_line, dtype=np.float64)
+    theta = np.ascontiguousarray(track.theta_track, dtype=np.float64)
+    if centre.ndim != 2 or centre.shape[0] != 2 or theta.shape != (centre.shape[1],):
+        raise ValueError(f"track: center_line {centre.shape} and theta_track {theta.shape} must be "
+                         "[2, n] and [n]")
+    return centre, theta, float(track.track_length), float(track.track_width)
+
+
 def _left_normal(t):
     t = np.asarray(t, dtype=np.float64)
     n = np.array([-t[1], t[0]])

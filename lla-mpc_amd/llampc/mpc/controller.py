@@ -155,6 +155,21 @@ class CandidateGenerator:
         return np.ascontiguousarray(U)
 
 
+def check_corridor_args(track, weight, margin):
+    """What LLAMPC / DeviceController refuse of a corridor before any device call: a weight that is
+    negative or not finite; with a weight, a track without the corridor's tables or a margin that
+    leaves no corridor (setupNLP(device_corridor=True)'s checks and messages)."""
+    w = float(weight)
+    if not (np.isfinite(w) and w >= 0):
+        raise ValueError("corridor_weight must be finite and >= 0")
+    if w > 0:
+        from llampc.mpc import constraints
+        constraints.require_track(track, "corridor_weight > 0")
+        constraints.require_margin(track, margin)
+        if not np.isfinite(float(margin)):
+            raise ValueError(f"corridor_margin {margin} must be finite")
+
+
 class DeviceController:
     """Handle of llampc_ctl (include/llampc.h): the control step of rt.py:278-366 as ONE launch
     on the bank's device, the controller state (x_{t-1}, u_{t-1}, the chosen sequence,
@@ -163,7 +178,8 @@ class DeviceController:
 
     def __init__(self, bank: ModelBank, track, H=20, C=64, K=10, Ts=0.02, v_factor=0.9, mu_init=1.0, S=20,
                  sigma=(0.05, 0.02), seed=2, nominal6=None, cost=None, nan_policy=nat.NAN_FIRST,
-                 debug_inputs=False, lap_projidx=None, prelaunch=False):
+                 debug_inputs=False, lap_projidx=None, prelaunch=False, corridor_weight=0.0, corridor_margin=0.0):
+        check_corridor_args(track, corridor_weight, corridor_margin)
         if getattr(bank, "raceline", None) is not track:
             bank.set_raceline(track)
         self.bank, self.track, self.H, self.C = bank, track, int(H), int(C)
@@ -193,8 +209,52 @@ class DeviceController:
         self._carrier = None                 # a ShardedBank whose process group carries the exchange
         self.transport = None                # the sharded exchange's transport (set_exchange)
         self.prelaunch = False
+        self.corridor_weight, self.corridor_margin = 0.0, float(corridor_margin)
+        self._has_track = False
+        if float(corridor_weight) > 0:
+            self.set_corridor(corridor_weight, corridor_margin)
         if prelaunch:
             self.set_prelaunch(True)
+
+    def set_corridor(self, weight, margin=None):
+        """The soft track corridor of the tick's look-ahead (llampc_ctl_set_corridor): from the next
+        tick on every rolled-out cost gains ``weight`` times the summed squared slacks of its positions
+        on the track's half-planes (half width track_width / 2 - margin) along the previous tick's
+        chosen rollout shifted one step; the first tick after switching on uses the disabled corridor.
+        weight 0 switches it off: the plain tick again.  margin None keeps the current margin.  The
+        track's tables (center_line, theta_track, track_length, track_width) are uploaded on first use."""
+        margin = self.corridor_margin if margin is None else margin
+        check_corridor_args(self.track, weight, margin)
+        lib = nat.load()
+        if float(weight) > 0 and not self._has_track:
+            from llampc.mpc import constraints
+            centre, theta, length, width = constraints.track_tables(self.track)
+            nat.check(lib.llampc_ctl_set_track(self._h, centre.ctypes.data, theta.ctypes.data, centre.shape[1],
+                                               length, width))
+            self._has_track = True
+        if float(weight) > 0 or self._has_track:
+            nat.check(lib.llampc_ctl_set_corridor(self._h, float(weight), float(margin)))
+        self.corridor_weight, self.corridor_margin = float(weight), float(margin)
+
+    def corridor(self):
+        """The last tick's corridor (llampc_ctl_corridor; a corridor tick): (path [2, H+1] it was built
+        along, hp [H, 6], theta [H], valid).  With no valid path (tick 0, the first tick after the
+        corridor was switched on, a non-finite chosen rollout before): hp is constraints.disabled(H),
+        path and theta NaN."""
+        path, hp, theta = np.empty((2, self.H + 1)), np.empty((self.H, 6)), np.empty(self.H)
+        valid = nat.C.c_int32()
+        nat.check(nat.load().llampc_ctl_corridor(self._h, nat.dptr(path), nat.dptr(hp), nat.dptr(theta),
+                                                 nat.C.byref(valid)))
+        return path, hp, theta, bool(valid.value)
+
+    def corridor_costs(self):
+        """Every rolled-out cost of the last corridor tick (llampc_ctl_corridor_costs; debug_inputs):
+        [slots, C] in the record's slot order — the nominal model's one row while warm, else the
+        top-K's K rows and then the selection's; a slot without a model is NaN."""
+        out = np.empty((int(self.cfg.K) + 1, self.C))
+        n = nat.C.c_int32()
+        nat.check(nat.load().llampc_ctl_corridor_costs(self._h, nat.dptr(out), nat.C.byref(n)))
+        return out[:n.value].copy()
 
     def set_prelaunch(self, on=True):
         """Arm every next tick (llampc_ctl_set_prelaunch): its launch is enqueued behind the
@@ -376,10 +436,15 @@ class LLAMPC:
     def __init__(self, bank: ModelBank, track, H=20, Ts=0.02, K=10, C=64, v_factor=0.9,
                  mu_init=1.0, S=20, alpha=0.08, cost=None, integrator="rk4", seed=2,
                  nan_policy=nat.NAN_FIRST, nominal: dict | None = None, mode="device",
-                 sigma=(0.05, 0.02), debug_inputs=False, prelaunch=True):
+                 sigma=(0.05, 0.02), debug_inputs=False, prelaunch=True, corridor_weight=0.0, corridor_margin=0.0):
         from llampc.params import ORCA
         if mode not in ("device", "host"):
             raise ValueError(f"mode={mode!r}: 'device' or 'host'")
+        check_corridor_args(track, corridor_weight, corridor_margin)
+        if float(corridor_weight) > 0 and mode != "device":
+            raise ValueError("corridor_weight needs mode='device' (the corridor is built inside the tick's launch)")
+        if float(corridor_weight) > 0 and hasattr(bank, "params_global") and hasattr(bank, "bank"):
+            raise ValueError("corridor_weight: a sharded controller has no corridor ticks")
         self.mode = mode
         # a ShardedBank: this rank's controller over its shard, exchanging the selection with the
         # other ranks every tick (device mode; BASELINE config 5 across GPUs)
@@ -400,7 +465,8 @@ class LLAMPC:
             self._ctl = DeviceController(bank, track, H=H, C=C, K=K, Ts=Ts, v_factor=v_factor, mu_init=mu_init,
                                          S=S, sigma=sigma, seed=seed, nominal6=col[:, 0],
                                          cost=cost if cost is not None else nat.cost_struct(enforce_bounds=True),
-                                         nan_policy=nan_policy, debug_inputs=debug_inputs)
+                                         nan_policy=nan_policy, debug_inputs=debug_inputs,
+                                         corridor_weight=corridor_weight, corridor_margin=corridor_margin)
             if sharded is not None and sharded.exchange:
                 self._ctl.set_exchange(sharded)
                 if prelaunch and self._ctl.transport == "peer":
@@ -446,6 +512,29 @@ class LLAMPC:
             if on and not self._ctl.prelaunch:
                 self.bank.set_stream(None)
         self._ctl.set_prelaunch(on)
+
+    def set_corridor(self, weight, margin=None):
+        """Device mode: the tick's soft track corridor on (weight > 0) or off (0) from the next tick
+        (DeviceController.set_corridor)."""
+        if self._ctl is None:
+            if float(weight) > 0:
+                raise ValueError("corridor_weight needs mode='device' (the corridor is built inside the tick's launch)")
+            return
+        self._ctl.set_corridor(weight, margin)
+
+    def corridor(self):
+        """Device mode, after a corridor tick: (path [2, H+1], hp [H, 6], theta [H], valid) of the last
+        tick's corridor (DeviceController.corridor)."""
+        if self._ctl is None:
+            raise nat.NativeError("corridor() needs mode='device'")
+        return self._ctl.corridor()
+
+    def corridor_costs(self):
+        """Device mode with debug_inputs=True, after a corridor tick: every rolled-out cost [slots, C]
+        (DeviceController.corridor_costs)."""
+        if self._ctl is None:
+            raise nat.NativeError("corridor_costs() needs mode='device'")
+        return self._ctl.corridor_costs()
 
     def device_us(self) -> float:
         """Device mode: the last tick's device time (DeviceController.device_us); else NaN."""

@@ -116,14 +116,8 @@ class setupNLP:
         self.max_slack = 0.0         # the last corridor solve's largest slack along xmpc
         self.device_corridor, self.corridor_margin = bool(device_corridor), float(corridor_margin)
         if self.device_corridor:
-            missing = [k for k in ("center_line", "theta_track", "track_length", "track_width")
-                       if getattr(track, k, None) is None]
-            if track is None or missing:
-                raise ValueError("device_corridor=True needs a track with center_line, theta_track, track_length "
-                                 f"and track_width (missing: {'the track' if track is None else ', '.join(missing)})")
-            if not self.corridor_margin < float(track.track_width) / 2:      # a NaN margin too
-                raise ValueError(f"corridor_margin {corridor_margin} leaves no corridor "
-                                 f"(track width {track.track_width})")
+            constraints.require_track(track, "device_corridor=True")
+            constraints.require_margin(track, corridor_margin)
         self.last_corridor = None    # the last device-built corridor [H, 6]
         self._last_xmpc = None       # the last solve's positions [2, H+1] (constraints.default_path)
         self.horizon, self.Ts = int(horizon), float(Ts)
@@ -162,14 +156,9 @@ class setupNLP:
                     "theta": np.zeros(H)}
         self._addr = {k: v.ctypes.data for k, v in self._io.items()}
         if self.device_corridor:
-            tr = self.track
-            centre = np.ascontiguousarray(tr.center_line, dtype=np.float64)
-            theta = np.ascontiguousarray(tr.theta_track, dtype=np.float64)
-            if centre.ndim != 2 or centre.shape[0] != 2 or theta.shape != (centre.shape[1],):
-                raise ValueError(f"track: center_line {centre.shape} and theta_track {theta.shape} must be "
-                                 "[2, n] and [n]")
+            centre, theta, length, width = constraints.track_tables(self.track)
             nat.check(nat.load().llampc_nlp_set_track(h, centre.ctypes.data, theta.ctypes.data, centre.shape[1],
-                                                      float(tr.track_length), float(tr.track_width)))
+                                                      length, width))
 
     def _path(self, path):
         """A corridor path as the library takes it: [2, H+1], finite (checked before the library)."""
