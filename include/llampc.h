@@ -172,7 +172,8 @@ int llampc_bank_reset(llampc_bank* bank);                 /* empty the window   
 /* plan-kernel launches enqueued on this bank so far (every tick entry point is ONE
  * launch; the controller test counts them — replaces nothing in the reference).  On an NLP
  * solver's bank: its solve launches, and every track-corridor kernel (llampc_nlp_solve_track,
- * llampc_nlp_track_corridor) as one more */
+ * llampc_nlp_track_corridor, llampc_nlp_batch_solve_track, llampc_nlp_batch_track_corridor) as one
+ * more */
 int llampc_bank_launches(const llampc_bank* bank, int64_t* launches);
 /* ring: [n][W] oldest -> newest (the rt.py error_windows layout, zeros if unfilled) */
 int llampc_bank_window(llampc_bank* bank, double* ring, int32_t* window_count);
@@ -202,8 +203,8 @@ int llampc_bank_set_concurrency(llampc_bank* bank, int32_t banks);
  * count = launches timed. */
 int llampc_bank_timing(llampc_bank* bank, int32_t enable, int32_t max_launches);
 /* Synchronises, returns avg_ms[3] and count[3] for {plan kernel, the NLP solver's track-corridor
- * kernel (llampc_nlp_track_corridor, llampc_nlp_solve_track), reserved} since the last read, and
- * re-arms the counters. */
+ * kernel (llampc_nlp_track_corridor, llampc_nlp_solve_track and their llampc_nlp_batch_* forms),
+ * reserved} since the last read, and re-arms the counters. */
 int llampc_bank_timing_read(llampc_bank* bank, double* avg_ms, int64_t* count);
 
 /* ---- look-back (host pointers) -------------------------------------------------- */
@@ -651,6 +652,45 @@ enum llampc_nlp_status { LLAMPC_NLP_OK = 0,
 int llampc_nlp_batch_solve(llampc_nlp_batch* nb, int32_t B, const int64_t* model_idx, const uint64_t* seed,
                            const double* x0, const double* xref, const double* uprev, const double* base,
                            const int32_t* has_hold, double* umpc, double* fval, double* xmpc, int32_t* status);
+/* llampc_nlp_batch_solve under a soft corridor per problem (csrc/nlp_batch_corr.hip), still ONE
+ * launch: hp [B][H][6], problem p's half-planes as llampc_nlp_solve_corridor takes them (a problem
+ * that wants none passes rows (0, 0, +inf, 0, 0, +inf)), and weight [B], problem p's own.  Problem
+ * p's search is llampc_nlp_solve_corridor's with hp[p] and weight[p], bit for bit; with every
+ * half-plane disabled it is llampc_nlp_batch_solve's.  fval includes the penalty.  -> max_slack [B]:
+ * the largest slack along problem p's returned xmpc on hp[p], computed on the host; 0 for a problem
+ * whose status is not LLAMPC_NLP_OK.  The corridors travel in a pinned mapped buffer of their own;
+ * the problems' records are llampc_nlp_batch_solve's.  LLAMPC_E_ARG, with nothing launched and the
+ * launch counter unchanged: what llampc_nlp_batch_solve refuses, hp, weight or max_slack NULL, and
+ * for any problem (its index is in the message) a non-finite normal component, an offset NaN or
+ * -inf, a weight negative or non-finite.  The call number advances as llampc_nlp_batch_solve's
+ * does.  Blocking. */
+int llampc_nlp_batch_solve_corridor(llampc_nlp_batch* nb, int32_t B, const int64_t* model_idx, const uint64_t* seed,
+                                    const double* x0, const double* xref, const double* uprev, const double* base,
+                                    const int32_t* has_hold, const double* hp /* [B][H][6] */,
+                                    const double* weight /* [B] */, double* umpc, double* fval, double* xmpc,
+                                    int32_t* status, double* max_slack /* [B] */);
+/* The track for the device-built corridors, as llampc_nlp_set_track takes it (the same checks).
+ * One track per solver: two tracks are two solvers, or host-built hp.  Blocking. */
+int llampc_nlp_batch_set_track(llampc_nlp_batch* nb, const double* centre /* [2][n] */,
+                               const double* theta /* [n] */, int32_t n, double track_length, double track_width);
+/* The track's corridors along B paths on the device (csrc/corridor_batch.hip: one kernel of B x H
+ * blocks): path [B][2][H+1] -> hp [B][H][6] and theta [B][H] (may be NULL), each problem's as
+ * llampc_nlp_track_corridor builds them.  LLAMPC_E_STATE with no track set; LLAMPC_E_ARG, with
+ * nothing launched: B < 1 or B > max_batch, a non-finite path entry (the problem is named), a
+ * margin that is not finite or >= track_width / 2.  Blocking. */
+int llampc_nlp_batch_track_corridor(llampc_nlp_batch* nb, int32_t B, const double* path /* [B][2][H+1] */,
+                                    double margin, double* hp /* [B][H][6] */, double* theta /* [B][H] or NULL */);
+/* llampc_nlp_batch_solve_corridor with the track's corridors along the problems' paths, built on
+ * the device: the corridor kernel, then the search, on the bank's stream with no host
+ * synchronisation between the two and one wait for the B tags (two launches).  -> max_slack [B] on
+ * the built half-planes, hp_out [B][H][6] (may be NULL) a copy of them.  LLAMPC_E_STATE and
+ * LLAMPC_E_ARG as llampc_nlp_batch_track_corridor and llampc_nlp_batch_solve_corridor (weights);
+ * LLAMPC_E_DEVICE if a read-back corridor is not a valid one.  Blocking. */
+int llampc_nlp_batch_solve_track(llampc_nlp_batch* nb, int32_t B, const int64_t* model_idx, const uint64_t* seed,
+                                 const double* x0, const double* xref, const double* uprev, const double* base,
+                                 const int32_t* has_hold, const double* path /* [B][2][H+1] */, double margin,
+                                 const double* weight /* [B] */, double* umpc, double* fval, double* xmpc,
+                                 int32_t* status, double* max_slack /* [B] */, double* hp_out /* [B][H][6] or NULL */);
 int llampc_nlp_batch_destroy(llampc_nlp_batch* nb);
 
 /* ---- raw batched dynamics (Dynamic API parity) ---------------------------------- */

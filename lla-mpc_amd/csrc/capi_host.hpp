@@ -216,6 +216,73 @@ inline const char* nlp_batch_args_invalid(int32_t B, int32_t max_batch, const in
   return nullptr;
 }
 
+// The batched corridor solve's buffers (llampc_nlp_batch_solve_corridor / _solve_track; nlp.hpp
+// NlpBatchCorridor): per problem one part of the pinned mapped corridor buffer, doubles hp [HMAX][6]
+// (rows 0..H-1 used) | theta [HMAX] at theta_off (the device builder's) | the problem's weight at
+// w_off, padded to whole 64-byte lines; and one path [2][H+1] of the pinned mapped path buffer,
+// padded likewise.  The problems' records (nlp_batch_layout) are untouched.
+struct NlpBatchCorLayout {
+  size_t cor_doubles, theta_off, w_off, path_doubles;
+};
+inline NlpBatchCorLayout nlp_batch_cor_layout() {
+  NlpBatchCorLayout c;
+  c.theta_off = 6 * (size_t)LLAMPC_HMAX;
+  c.w_off = c.theta_off + (size_t)LLAMPC_HMAX;
+  c.cor_doubles = (c.w_off + 1 + 7) / 8 * 8;
+  c.path_doubles = (2 * ((size_t)LLAMPC_HMAX + 1) + 7) / 8 * 8;
+  return c;
+}
+inline NlpBatchCorridor nlp_batch_cor_arg(const NlpBatch& bt, const NlpBatchCorLayout& c, const double* cor) {
+  NlpBatchCorridor a{};
+  a.bt = bt;
+  a.cor = cor;
+  a.cor_doubles = (uint32_t)c.cor_doubles;
+  a.w_off = (uint32_t)c.w_off;
+  return a;
+}
+
+// One problem's part (cor_doubles doubles at `part`): its weight, and its half-planes hp [H][6] — or,
+// hp null, NaN in the rows and theta entries the device builder is about to write, so that a row it
+// did not write fails corridor_invalid afterwards.
+inline void nlp_batch_cor_pack(const NlpBatchCorLayout& c, int32_t H, double* part, const double* hp, double weight) {
+  if (hp) {
+    std::memcpy(part, hp, 6 * (size_t)H * sizeof(double));
+  } else {
+    for (int i = 0; i < 6 * H; ++i) part[i] = __builtin_nan("");
+    for (int i = 0; i < H; ++i) part[c.theta_off + i] = __builtin_nan("");
+  }
+  part[c.w_off] = weight;
+}
+
+// What the batched corridor entries refuse, per problem, before anything is written or launched:
+// null if valid, else what is wrong with the first bad problem, its index included (in buf).
+// hp [B][H][6] or null (the device-built corridor: the weights alone), weight [B].
+inline const char* nlp_batch_corridor_invalid(int32_t B, int32_t H, const double* hp, const double* weight, char* buf,
+                                              size_t nbuf) {
+  if (!weight) return "weight is NULL";
+  for (int32_t q = 0; q < B; ++q) {
+    const double one[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (const char* why = hp ? corridor_invalid(hp + 6 * (size_t)H * q, H, weight[q]) : corridor_invalid(one, 1, weight[q]))
+      return (std::snprintf(buf, nbuf, "problem %d: %s", q, why), buf);
+  }
+  return nullptr;
+}
+
+// The paths [B][2][H+1] of a device-built batch: finite.  Null if valid (else in buf, with the problem).
+inline const char* nlp_batch_paths_invalid(int32_t B, int32_t H, const double* path, char* buf, size_t nbuf) {
+  for (int32_t q = 0; q < B; ++q)
+    for (int i = 0; i < 2 * (H + 1); ++i)
+      if (!std::isfinite(path[2 * (size_t)(H + 1) * q + i]))
+        return (std::snprintf(buf, nbuf, "problem %d: path entry %d is not finite", q, i), buf);
+  return nullptr;
+}
+
+// A problem's max_slack: corridor_max_slack of its returned trajectory; 0 for a problem whose tag
+// did not arrive or that found no finite objective (its trajectory is not a solution's).
+inline double nlp_batch_slack(bool arrived, int32_t best_it, const double* hp, const double* traj, int32_t H) {
+  return arrived && best_it >= 0 ? corridor_max_slack(hp, traj, H) : 0.0;
+}
+
 // The polled completion's wait bound in s_memrealtime ticks (100 MHz): a 2 s floor plus
 // 40 ns per look-ahead rollout step of the launch (a rate floor of 2.5e7 steps/s, ~10^3
 // below the fast path's, so the general-path re-runs, the raceline walker and launches

@@ -125,4 +125,27 @@ static_assert(sizeof(NlpBatch) == 40 && alignof(NlpBatch) == 8, "NlpBatch layout
 // B x nl blocks, all co-resident (the caller has checked B nl against the CU count)
 hipError_t launch_nlp_batch(const NlpLaunch& a, const NlpBatch& bt, int B, hipStream_t s);
 
+// The batched corridor solve's own argument (llampc_nlp_batch_solve_corridor / _solve_track;
+// nlp_batch_corr.hip): the batch's, unchanged, and the problems' corridors in a buffer of their own
+// (the device alias of a pinned mapped buffer, as NlpCorridor.hp): problem p's half-planes hp [H][6]
+// start at cor + p cor_doubles, its own weight is the double at w_off of its part (after the
+// half-planes, then the device builder's theta: capi_host.hpp nlp_batch_cor_layout).  Each block
+// copies its problem's half-planes once into its LDS and takes the weight, block-uniform, into
+// scalar registers.
+struct NlpBatchCorridor {
+  NlpBatch bt;
+  const double* cor;
+  uint32_t cor_doubles, w_off;
+};
+static_assert(sizeof(NlpBatchCorridor) == 56 && alignof(NlpBatchCorridor) == 8, "NlpBatchCorridor layout (a kernel argument)");
+// B x nl blocks, all co-resident, as launch_nlp_batch; LDS as the corridor solve's
+hipError_t launch_nlp_batch_corridor(const NlpLaunch& a, const NlpBatchCorridor& bc, int B, hipStream_t s);
+
+// The track corridor along B paths (track_corridor_batch_kernel, corridor_batch.hip): B x H blocks,
+// block (p, k) writes row k - 1 of problem p's half-planes at cor + p cor_doubles and theta_k at
+// theta_off of that part, along path + p path_doubles ([2][H+1]; the device alias of a pinned mapped
+// buffer, as cor is).
+hipError_t launch_track_corridor_batch(const TrackK& t, const double* path, uint32_t path_doubles, int32_t B, int32_t H,
+                                       double hw, double* cor, uint32_t cor_doubles, uint32_t theta_off, hipStream_t s);
+
 }  // namespace llampc

@@ -723,7 +723,9 @@ __host__ __device__ __forceinline__ size_t nlp_traj_off(int H, int nl, int elite
 // after them), the rollouts' objective with the corridor term (rollout_dev.hpp kRCorr), or one
 // NlpBatch, the batched solve's (BATCH, nlp_batch.hip): the grid is B x nl blocks, block g is
 // block g % nl of problem g / nl, whose words (lists, sequences, state, result, host tag) and
-// inputs (its record in the pinned buffer, in place of pk) are its own.
+// inputs (its record in the pinned buffer, in place of pk) are its own; or one NlpBatchCorridor
+// (COR and BATCH, nlp_batch_corr.hip): the batch's argument and, per problem, its own half-planes
+// and weight from the corridor buffer (nlp_cor below) — the rest is the text of the two.
 namespace {
 __device__ __forceinline__ NlpCorridor nlp_cor() { return NlpCorridor{nullptr, 0.0}; }
 __device__ __forceinline__ NlpCorridor nlp_cor(NlpCorridor c) { return c; }
@@ -735,12 +737,19 @@ __device__ __forceinline__ NlpBatch nlp_bat(T...) { return NlpBatch{}; }
 __device__ __forceinline__ uint64_t nlp_uni_word(const uint64_t* p) {
   return (uint64_t)__double_as_longlong(nlp_uni(__longlong_as_double((long long)*p)));
 }
+// NlpBatchCorridor: the batch's argument as it is, and the block's problem's corridor — its
+// half-planes' address and its own weight (block-uniform, into scalar registers)
+__device__ __forceinline__ NlpBatch nlp_bat(const NlpBatchCorridor& c) { return c.bt; }
+__device__ __forceinline__ NlpCorridor nlp_cor(const NlpBatchCorridor& c) {
+  const double* hp = c.cor + (size_t)(blockIdx.x >> c.bt.nl_log2) * c.cor_doubles;
+  return NlpCorridor{hp, __longlong_as_double((long long)nlp_uni_word(reinterpret_cast<const uint64_t*>(hp + c.w_off)))};
+}
 }  // namespace
 template <bool ST, int NT, class... Ext>
 __global__ __launch_bounds__(NT) void nlp_kernel(NlpLaunch a, NlpInline pk, Ext... extv) {
-  constexpr bool COR = (std::is_same_v<Ext, NlpCorridor> || ...);
-  constexpr bool BATCH = (std::is_same_v<Ext, NlpBatch> || ...);
-  static_assert(sizeof...(Ext) <= 1, "at most the corridor's or the batch's argument");
+  constexpr bool COR = ((std::is_same_v<Ext, NlpCorridor> || std::is_same_v<Ext, NlpBatchCorridor>) || ...);
+  constexpr bool BATCH = ((std::is_same_v<Ext, NlpBatch> || std::is_same_v<Ext, NlpBatchCorridor>) || ...);
+  static_assert(sizeof...(Ext) <= 1, "at most the corridor's, the batch's or the batched corridor's argument");
   [[maybe_unused]] const NlpCorridor cor = nlp_cor(extv...);
   [[maybe_unused]] const NlpBatch bt = nlp_bat(extv...);
   [[maybe_unused]] const uint64_t* rec = nullptr;      // BATCH: the problem's input record

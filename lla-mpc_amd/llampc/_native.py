@@ -206,6 +206,15 @@ _SIGNATURES = {
     # B, model_idx [B] (int64), seed [B] (uint64) or NULL, x0, xref, uprev, base or NULL, has_hold [B]
     # (int32) -> umpc, fval, xmpc, status [B] (int32)
     "llampc_nlp_batch_solve": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 11),
+    # llampc_nlp_batch_solve's, with hp [B][H][6], weight [B] after has_hold and max_slack [B] last
+    "llampc_nlp_batch_solve_corridor": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 14),
+    "llampc_nlp_batch_set_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double]),
+    # B, path [B][2][H+1], margin -> hp [B][H][6], theta [B][H] (or NULL)
+    "llampc_nlp_batch_track_corridor": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p,
+                                                  C.c_void_p]),
+    # llampc_nlp_batch_solve_corridor's, with path [B][2][H+1], margin in hp's place and hp_out last
+    "llampc_nlp_batch_solve_track": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.c_double] +
+                                     [C.c_void_p] * 7),
     "llampc_nlp_batch_destroy": (C.c_int, [C.c_void_p]),
     "llampc_dynamics_batch": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.POINTER(Vehicle), C.c_int64, C.c_void_p, C.c_int32,

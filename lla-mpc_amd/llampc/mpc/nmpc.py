@@ -278,13 +278,36 @@ class setupNLPBatch:
     issued as consecutive launches of as many problems as fit.  Chunking changes no result bit of a
     first solve; each chunk consumes one solve number (the Philox call word), and the chunk counts
     follow from the shapes alone, so call numbers stay deterministic: problem p of a chunked solve
-    is in chunk p // per_launch, whose number is the count of launches before it."""
+    is in chunk p // per_launch, whose number is the count of launches before it.
+
+    Corridors (module doc) are per problem: ``solve(..., corridor=hp [B, H, 6], corridor_weight=w [B])``
+    keeps the batch one launch, every problem with its own half-planes and weight
+    (csrc/nlp_batch_corr.hip).  ``setupNLPBatch(..., track=t, device_corridor=True,
+    corridor_margin=m)`` builds the track's corridors on the device along ``corridor_path``
+    [B, 2, H+1] (one kernel of B x H blocks ahead of the search on the same stream), and
+    ``track_corridor(paths)`` is that builder alone.  One track per solver: cars on two tracks take
+    two solvers, or host-built ``corridor=``.  The horizon is at most LLAMPC_HMAX = 64."""
 
     def __init__(self, horizon, Ts, Q, P, R, params, bank, max_batch=8, samples=1024, iters=8, elite=32,
-                 sigma=(0.3, 0.15), std_floor=1e-4, seed=0, max_resident=None):
+                 sigma=(0.3, 0.15), std_floor=1e-4, seed=0, max_resident=None, *, track=None, corridor_weight=1e4,
+                 corridor_tol=1e-4, device_corridor=False, corridor_margin=0.0):
         if not isinstance(bank, ModelBank):
             raise TypeError("bank must be a ModelBank")
         self.horizon, self.Ts = int(horizon), float(Ts)
+        if not 1 <= self.horizon <= nat.HMAX:
+            raise ValueError(f"horizon must lie in [1, {nat.HMAX}], got {horizon}")
+        self.corridor_weight, self.corridor_tol = float(corridor_weight), float(corridor_tol)
+        if not (np.isfinite(self.corridor_weight) and self.corridor_weight >= 0):
+            raise ValueError("corridor_weight must be finite and >= 0")
+        self.track = track
+        self.device_corridor, self.corridor_margin = bool(device_corridor), float(corridor_margin)
+        if self.device_corridor:
+            constraints.require_track(track, "device_corridor=True")
+            constraints.require_margin(track, corridor_margin)
+        self.max_slack = None        # the last corridor solve's largest slack along each xmpc [B]
+        self.violation = None        # ... Ts where it exceeds corridor_tol, else 0.0 [B]
+        self.last_corridor = None    # the last device-built corridors [B, H, 6]
+        self._last_xmpc = {}         # slot -> its last solve's positions [2, H+1] (constraints.default_path)
         self.params, self.bank, self.max_batch = params, bank, int(max_batch)
         self.samples, self.iters, self.elite = int(samples), int(iters), int(elite)
         self.sigma = np.asarray(sigma, dtype=np.float64)
@@ -306,20 +329,74 @@ class setupNLPBatch:
             raise ValueError(f"max_resident={self.max_resident} holds no problem ({nl} blocks each)")
         self.per_launch = min(self.max_batch, self.max_resident // nl)     # problems per launch
         self._last = {}              # slot -> previous umpc [H, 2] (absent: cold)
+        if self.device_corridor:
+            centre, theta, length, width = constraints.track_tables(track)
+            try:
+                nat.check(nat.load().llampc_nlp_batch_set_track(h, centre.ctypes.data, theta.ctypes.data,
+                                                                centre.shape[1], length, width))
+            except Exception:
+                self.close()
+                raise
 
     def reset(self, slots=None):
-        """Drops the warm starts of ``slots`` (None: all)."""
+        """Drops the warm starts (and the default corridor paths) of ``slots`` (None: all)."""
         if slots is None:
             self._last.clear()
+            self._last_xmpc.clear()
         else:
             for p in slots:
                 self._last.pop(int(p), None)
+                self._last_xmpc.pop(int(p), None)
 
-    def solve(self, models, x0, xref, uprev, seeds=None):
+    def _paths(self, paths, B):
+        """Corridor paths as the library takes them: [B, 2, H+1], finite (checked before the library)."""
+        H = self.horizon
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        if paths.shape != (B, 2, H + 1):
+            raise ValueError(f"corridor_path must be [B, 2, H+1] = {(B, 2, H + 1)}, got {paths.shape}")
+        if not np.all(np.isfinite(paths)):
+            raise ValueError("corridor_path must be finite")
+        return paths
+
+    def track_corridor(self, paths, margin=None):
+        """The track's corridors along ``paths`` [B, 2, H+1] built on the device
+        (llampc_nlp_batch_track_corridor, chunks of max_batch): -> (hp [B, H, 6], theta [B, H]), each
+        problem's constraints.track_corridor(track, paths[p], margin) and track.xy_to_param of its
+        points to 1e-12.  margin: None = corridor_margin.  Needs device_corridor=True."""
+        if not self.device_corridor:
+            raise ValueError("track_corridor needs setupNLPBatch(..., device_corridor=True)")
+        if self._h is None:
+            raise nat.NativeError("solver is closed")
+        paths = np.asarray(paths, dtype=np.float64)
+        if paths.ndim != 3:
+            raise ValueError(f"paths must be [B, 2, H+1], got {paths.shape}")
+        B, H = paths.shape[0], self.horizon
+        paths = self._paths(paths, B)
+        m = self.corridor_margin if margin is None else float(margin)
+        constraints.require_margin(self.track, m)
+        hp, theta = np.zeros((B, H, 6)), np.zeros((B, H))
+        for lo in range(0, B, self.max_batch):
+            hi = min(B, lo + self.max_batch)
+            nat.check(nat.load().llampc_nlp_batch_track_corridor(self._h, hi - lo, paths[lo:hi].ctypes.data, m,
+                                                                 hp[lo:hi].ctypes.data, theta[lo:hi].ctypes.data))
+        return hp, theta
+
+    def solve(self, models, x0, xref, uprev, seeds=None, corridor=None, corridor_weight=None, corridor_path=None):
         """models [B] bank indices, x0 [B, 6], xref [B, 2, H+1] (or [2, H+1] shared), uprev [B, 2],
         seeds [B] (None: the solver's seed for all) -> (umpc [B, 2, H], fval [B], xmpc [B, 6, H+1],
         ok [B]).  A problem that found no finite objective, or whose completion never arrived, has
-        ok False, umpc zeros and fval inf, and does not disturb the others."""
+        ok False, umpc zeros and fval inf, and does not disturb the others.
+
+        corridor: None, or the problems' half-planes [B, H, 6] ([H, 6]: shared; a problem that wants
+        none takes constraints.disabled(H)), each with its own corridor_weight (a scalar or [B];
+        None: the solver's) — still one launch (llampc_nlp_batch_solve_corridor); problem p is then
+        setupNLP.solve(..., corridor=corridor[p]) with that weight, bit for bit.  With
+        device_corridor=True and no corridor: the track's corridors, built on the device ahead of
+        the search (llampc_nlp_batch_solve_track), along corridor_path [B, 2, H+1], or per slot along
+        constraints.default_path (the slot's previous xmpc shifted one step; the ray from the car on
+        a cold slot).  After a corridor solve: max_slack [B], violation [B] (Ts where the slack
+        exceeds corridor_tol, else 0.0; both 0 for a failed problem) and, device-built,
+        last_corridor [B, H, 6]."""
         if self._h is None:
             raise nat.NativeError("solver is closed")
         H = self.horizon
@@ -347,6 +424,33 @@ class setupNLPBatch:
             seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
             if seeds.shape != (B,):
                 raise ValueError(f"seeds must be [B] = {(B,)}, got {seeds.shape}")
+        # the corridor's arguments: all checked before anything is launched
+        paths = None
+        if corridor is not None:
+            corridor = np.asarray(corridor, dtype=np.float64)
+            if corridor.shape == (H, 6):
+                corridor = np.broadcast_to(corridor, (B, H, 6))
+            if corridor.shape != (B, H, 6):
+                raise ValueError(f"corridor must be [B, H, 6] = {(B, H, 6)} or [H, 6], got {corridor.shape}")
+            corridor = np.ascontiguousarray(corridor)
+        elif corridor_path is not None:
+            if not self.device_corridor:
+                raise ValueError("corridor_path needs setupNLPBatch(..., track=..., device_corridor=True)")
+            paths = self._paths(corridor_path, B)
+        elif self.device_corridor:
+            paths = self._paths([constraints.default_path(x0[p], H, self.Ts, self._last_xmpc.get(p))
+                                 for p in range(B)], B)
+        with_corridor = corridor is not None or paths is not None
+        if with_corridor or corridor_weight is not None:
+            w = self.corridor_weight if corridor_weight is None else corridor_weight
+            w = np.asarray(w, dtype=np.float64)
+            if w.shape == ():
+                w = np.broadcast_to(w, (B,))
+            if w.shape != (B,):
+                raise ValueError(f"corridor_weight must be a scalar or [B] = {(B,)}, got {w.shape}")
+            if not (np.all(np.isfinite(w)) and np.all(w >= 0)):
+                raise ValueError("corridor_weight must be finite and >= 0")
+            weights = np.ascontiguousarray(w)
         hold = np.array([p in self._last for p in range(B)], dtype=np.int32)
         base = np.zeros((B, H, 2))
         for p in range(B):
@@ -355,20 +459,42 @@ class setupNLPBatch:
                 base[p, -1] = self._last[p][-1]
         umpc, fval = np.zeros((B, H, 2)), np.zeros(B)
         xmpc, status = np.zeros((B, H + 1, 6)), np.zeros(B, dtype=np.int32)
+        slack = np.zeros(B)
+        built = np.zeros((B, H, 6)) if paths is not None else None
         lib = nat.load()
         for lo in range(0, B, self.per_launch):
             hi = min(B, lo + self.per_launch)
-            nat.check(lib.llampc_nlp_batch_solve(
-                self._h, hi - lo, models[lo:hi].ctypes.data, seeds[lo:hi].ctypes.data, x0[lo:hi].ctypes.data,
-                xref[lo:hi].ctypes.data, uprev[lo:hi].ctypes.data, base[lo:hi].ctypes.data, hold[lo:hi].ctypes.data,
-                umpc[lo:hi].ctypes.data, fval[lo:hi].ctypes.data, xmpc[lo:hi].ctypes.data, status[lo:hi].ctypes.data))
+            ins = (self._h, hi - lo, models[lo:hi].ctypes.data, seeds[lo:hi].ctypes.data, x0[lo:hi].ctypes.data,
+                   xref[lo:hi].ctypes.data, uprev[lo:hi].ctypes.data, base[lo:hi].ctypes.data, hold[lo:hi].ctypes.data)
+            outs = (umpc[lo:hi].ctypes.data, fval[lo:hi].ctypes.data, xmpc[lo:hi].ctypes.data, status[lo:hi].ctypes.data)
+            if corridor is not None:
+                nat.check(lib.llampc_nlp_batch_solve_corridor(*ins, corridor[lo:hi].ctypes.data, weights[lo:hi].ctypes.data,
+                                                              *outs, slack[lo:hi].ctypes.data))
+            elif paths is not None:
+                nat.check(lib.llampc_nlp_batch_solve_track(*ins, paths[lo:hi].ctypes.data, self.corridor_margin,
+                                                           weights[lo:hi].ctypes.data, *outs, slack[lo:hi].ctypes.data,
+                                                           built[lo:hi].ctypes.data))
+            else:
+                nat.check(lib.llampc_nlp_batch_solve(*ins, *outs))
         ok = status == nat.NLP_OK
         for p in range(B):
             if ok[p]:
                 self._last[p] = umpc[p].copy()
             else:
                 self._last.pop(p, None)
-        return np.ascontiguousarray(umpc.transpose(0, 2, 1)), fval, np.ascontiguousarray(xmpc.transpose(0, 2, 1)), ok
+        xm = np.ascontiguousarray(xmpc.transpose(0, 2, 1))
+        if self.device_corridor:
+            for p in range(B):
+                if ok[p]:
+                    self._last_xmpc[p] = xm[p, :2].copy()
+                else:
+                    self._last_xmpc.pop(p, None)
+        if with_corridor:
+            self.max_slack = slack
+            self.violation = np.where(ok & (slack > self.corridor_tol), self.Ts, 0.0)
+            if built is not None:
+                self.last_corridor = built
+        return np.ascontiguousarray(umpc.transpose(0, 2, 1)), fval, xm, ok
 
     def close(self):
         if self._h is not None:
