@@ -288,12 +288,54 @@ int llampc_plan(llampc_bank* bank, const llampc_plan_in* in, llampc_plan_out* ou
  * staging buffer (one host-to-device copy; a corridor tick's inputs never travel as kernel
  * arguments).  LLAMPC_E_ARG, with nothing enqueued and the launch counter unchanged: hp NULL,
  * do_lookahead 0, LLAMPC_RK6, LLAMPC_XREF_RACELINE, a corridor or weight as above.
- * Not yet under a corridor (the remaining steps): llampc_plan_async / _wait,
- * llampc_plan_device, llampc_plan_exchange and the sharded bank, the controller tick
- * (llampc_ctl_*), the work-queue and inline-pack layouts, RK6, the per-model raceline reference. */
+ * The corridor built on the device, tick after tick, with an async form: llampc_plan_track below.
+ * Not yet under a corridor (the remaining steps): llampc_plan_device,
+ * llampc_plan_exchange and the sharded bank, the sharded controller, the work-queue and inline-pack
+ * layouts, RK6, the per-model raceline reference. */
 int llampc_plan_corridor(llampc_bank* bank, const llampc_plan_in* in, const double* hp /* [H][6] */,
                          double weight, llampc_plan_out* out, double* err_out, double* wmean_out,
                          double* cost_out);
+
+/* ---- track tick: llampc_plan_corridor with the corridor built inside the launch ---------------- */
+/* Attach (replace) the track whose corridor llampc_plan_track builds: llampc_nlp_set_track's
+ * arguments and refusals (centre [2][n] finite, theta [n] from 0 strictly increasing, track_length
+ * beyond theta[n-1], track_width > 0, 2 <= n <= 4096; LLAMPC_E_STATE while an async tick is
+ * outstanding).  Copied to the device; invalidates the bank's path.  Replaces nothing in the
+ * reference (constraints.py builds the half-planes on the host). */
+int llampc_bank_set_track(llampc_bank* bank, const double* centre /* [2][n] */, const double* theta /* [n] */,
+                          int32_t n, double track_length, double track_width);
+/* Seeds the next track tick's path P [2][H+1] (row k of its corridor is built at P_k, k = 1..H);
+ * NULL invalidates the path (the next track tick then runs on the disabled rows).  LLAMPC_E_ARG: a
+ * non-finite entry, H outside [1, LLAMPC_HMAX]. */
+int llampc_bank_set_path(llampc_bank* bank, const double* path /* [2][H+1] or NULL */, int32_t H);
+/* llampc_plan_corridor whose half-planes the launch builds itself (still ONE launch): H corridor blocks
+ * compute hp [H][6] from the bank's track (llampc_bank_set_track; half-width track_width / 2 - margin)
+ * along the bank's path, the look-ahead blocks roll out under it with llampc_plan_corridor's cost J_c,
+ * and once the record is complete the launch re-runs the chosen (sel_model, sel_cand) rollout and keeps
+ * its positions on the device as the next tick's path: P_j = X_{j+1} for j < H, P_H = X_H
+ * (constraints.default_path's prev_xmpc rule).  The host builds no geometry and moves no path between
+ * ticks.  The path is offered to a tick only when its H is the tick's and it was written by the bank's
+ * immediately preceding launch, itself a track tick, or seeded by llampc_bank_set_path since; it was
+ * written valid only if the chosen cost and positions were finite, sel_owned = 1 and
+ * 0 <= sel_cand < C.  Any other launch on the bank, llampc_bank_reset and llampc_bank_set_track clear
+ * it.  Without a valid path every row is (0, 0, +inf, 0, 0, +inf): no corridor.
+ * LLAMPC_RK4 on the given xref, H <= LLAMPC_HMAX.  Both completion modes, as llampc_plan_corridor.
+ * With nothing enqueued and the launch counter unchanged: LLAMPC_E_STATE without a track or while an
+ * async tick is outstanding; LLAMPC_E_ARG for do_lookahead 0, LLAMPC_RK6, LLAMPC_EULER_NLP,
+ * LLAMPC_XREF_RACELINE, a weight negative or non-finite, a margin non-finite or >= track_width / 2. */
+int llampc_plan_track(llampc_bank* bank, const llampc_plan_in* in, double weight, double margin,
+                      llampc_plan_out* out, double* err_out, double* wmean_out, double* cost_out);
+/* llampc_plan_async for the track tick: completed by llampc_plan_wait. */
+int llampc_plan_track_async(llampc_bank* bank, const llampc_plan_in* in, double weight, double margin);
+/* The last track tick's read-back (blocking; for tests and logging): the path it used [2][H+1] (NaN
+ * without a valid one), the rows it built hp [H][6] and their arc lengths theta [H], whether the path
+ * was valid, and what it left for the next tick: next_path [2][H+1], next_valid, and next_cost, the
+ * re-run's cost (the record's sel_cost).  LLAMPC_E_STATE unless the bank's last launch was a track tick. */
+int llampc_bank_track_corridor(llampc_bank* bank, double* path, double* hp, double* theta, int32_t* valid,
+                               double* next_path, int32_t* next_valid, double* next_cost);
+/* llampc_plan_variant for a track tick on a centre line of track_n points — host only:
+ * out = {lpm, G, cpl, stage, nb_cor (the corridor blocks: H)}. */
+int llampc_plan_variant_track(int64_t n, int32_t C, int32_t H, int32_t share, int32_t track_n, int32_t out[5]);
 /* Host pointers; asynchronous (SURVEY.md §8b "_async" variant): the inputs are copied
  * into the bank's pinned staging buffer before the call returns (the caller may reuse
  * them), and the H2D copy and the plan kernel are enqueued on the bank's stream; the

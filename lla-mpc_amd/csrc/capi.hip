@@ -67,7 +67,7 @@ static void timing_free(llampc_bank* b) {
 // The tick on device pointers (capi_common.hpp).  Advances the window bookkeeping when a look-back runs.
 int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out, double* d_err, double* d_wmean,
                 double* d_cost, hipStream_t s, uint64_t* host_tag, uint64_t host_seq, const InlinePack* pk,
-                llampc_mailbox* px, llampc_plan_out* px_merged, const PlanCorridor* cor) {
+                llampc_mailbox* px, llampc_plan_out* px_merged, const PlanCorridor* cor, const TrackTick* tt) {
   const bool lb = in.do_lookback != 0;
   const bool la = in.do_lookahead != 0;
   const bool raceline = la && in.xref_mode == LLAMPC_XREF_RACELINE;
@@ -156,11 +156,41 @@ int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out
     f.px_bound = (uint32_t)poll_units(px->bound, UINT32_MAX);
   }
   f.wq = b->d_wq.get();
+  // the track tick: the read copy is the one the launch before wrote (or llampc_bank_set_path), the
+  // write copy the other; the half-plane words' own sequence
+  PlanTrack trk{};
+  const uint32_t tseq = tt ? next_seq(b->tseq) : b->tseq;
+  if (tt) {
+    const size_t tn = (size_t)b->tr_n, ps = 2 * (size_t)kPlanPathStride;
+    const double* d = b->d_track.get();
+    const int rd = b->trk_cur, wr = rd ^ 1;
+    double* st = b->d_trk.get();
+    int32_t* fl = b->d_trk_flags.get();
+    trk.trk = TrackK{d, d + tn, d + 2 * tn, b->tr_n, 0, b->tr_L};
+    trk.hw = b->tr_width / 2 - tt->margin;
+    trk.weight = tt->weight;
+    trk.hp_tag = b->d_hp_tag.get();
+    trk.path_rd = st + ps * rd;
+    trk.path_wr = st + ps * wr;
+    trk.valid_rd = fl + rd;
+    trk.valid_wr = fl + wr;
+    trk.cost_wr = st + 2 * ps + wr;
+    trk.dbg = st + 2 * ps + 2;
+    trk.dbg_valid = fl + 2;
+    trk.late = reinterpret_cast<uint32_t*>(fl + 3);
+    trk.seq = tseq;
+    trk.poll = (uint32_t)poll_units(poll_bound_ticks(b->n, in.C, in.H), INT32_MAX);
+    trk.path_ok = track_path_offered(b->trk_path, in.H) ? 1 : 0;
+  }
   {
     TimedLaunch tl(b, 0, s);
-    HIP_TRY(launch_plan(lb ? &lbl : nullptr, la ? &lal : nullptr, f, s, pk, b->share, cor));
+    HIP_TRY(launch_plan(lb ? &lbl : nullptr, la ? &lal : nullptr, f, s, pk, b->share, cor, tt ? &trk : nullptr));
   }
   b->seq = seq;
+  b->tseq = tseq;
+  if (tt) b->trk_cur ^= 1;
+  b->trk_path = track_path_next(b->trk_path, tt ? kPathTrackTick : kPathOtherLaunch, in.H);
+  b->trk_last_H = tt ? in.H : 0;
   if (px) px->seq = px_seq;
   b->launches++;
   if (lb) {
@@ -175,7 +205,7 @@ namespace {
 // plan_shape of a look-ahead alone, for what no bank decides: of n models (they matter to the LPM
 // only; a plan input's own questions take n = 1), with the inline pack or a corridor offered.
 PlanShape lookahead_shape(int64_t n, bool la, int32_t C, int32_t H, int32_t integrator, int32_t xref_mode,
-                          int32_t share, bool pack, bool corridor) {
+                          int32_t share, bool pack, bool corridor, int32_t track_n = 0) {
   PlanShapeIn s{};
   s.n = n;
   s.la = la;
@@ -186,6 +216,7 @@ PlanShape lookahead_shape(int64_t n, bool la, int32_t C, int32_t H, int32_t inte
   s.share = share;
   s.pack = pack;
   s.corridor = corridor;
+  s.track_n = track_n;
   return plan_shape(s, 0);
 }
 
@@ -229,18 +260,19 @@ bool host_completion() { return getenv("LLAMPC_SYNC_COMPLETION") == nullptr; }
 
 // The host-completion tick: the inputs inline or staged, the record into pinned host memory,
 // then tick number *seq into the tag (wait_host_tag).
-// hp: the corridor tick, whose inputs are always staged (the corridor rides with them).
+// hp: the corridor tick, whose inputs are always staged (the corridor rides with them).  tt: the track
+// tick, staged too (its launch takes device inputs).
 int plan_launch_host(llampc_bank* b, const llampc_plan_in* in, hipStream_t s, uint64_t* seq,
-                     const double* hp = nullptr, double weight = 0.0) {
+                     const double* hp = nullptr, double weight = 0.0, const TrackTick* tt = nullptr) {
   llampc_plan_in din = *in;
   InlinePack pk;
   PlanCorridor cor{nullptr, weight};
-  const bool inl = !hp && inline_inputs(in);
+  const bool inl = !hp && !tt && inline_inputs(in);
   if (inl) pack_into(in, pk.v);
   else if (int rc = stage_inputs(b, in, &din, s, hp, &cor.hp)) return rc;
   *seq = ++b->hseq;
   return plan_launch(b, din, b->host.rec.dev(), nullptr, nullptr, nullptr, s, b->host.tag.dev(), *seq,
-                     inl ? &pk : nullptr, nullptr, nullptr, hp ? &cor : nullptr);
+                     inl ? &pk : nullptr, nullptr, nullptr, hp ? &cor : nullptr, tt);
 }
 
 // After a tick whose record reports a device-side status (an in-launch wait gave up) or whose
@@ -402,6 +434,7 @@ int llampc_bank_reset(llampc_bank* b) {
   HIP_TRY(hipStreamSynchronize(b->stream));
   b->count = 0;
   b->slot = 0;
+  b->trk_path = track_path_next(b->trk_path, kPathClear);
   return LLAMPC_OK;
 }
 
@@ -524,16 +557,41 @@ static int check_corridor_mode(const llampc_plan_in* in) {
   return LLAMPC_OK;
 }
 
-// llampc_plan (hp null) and llampc_plan_corridor: the blocking host-pointer tick.
+// What a track tick refuses before anything is enqueued (llampc_plan_track, llampc_plan_track_async; the
+// caller holds b->mu): no track, an async tick outstanding (LLAMPC_E_STATE), then plan_shape's refusals
+// of the track tick's modes, in its words, and a weight or margin track_tick_invalid names.
+static int check_track_tick(const llampc_bank* b, const llampc_plan_in* in, const TrackTick& tt) {
+  if (!b->tr_n) return fail(LLAMPC_E_STATE, "no track set: call llampc_bank_set_track first");
+  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding: call llampc_plan_wait");
+  if (in) {
+    const char* why = lookahead_shape(1, in->do_lookahead != 0, in->C, in->H, in->integrator, in->xref_mode, 1, false,
+                                      false, b->tr_n).refuse;
+    if (why == kNoTrackLookahead || why == kNoTrackRk6 || why == kNoTrackEuler || why == kNoTrackRaceline)
+      return fail(LLAMPC_E_ARG, "%s", why);
+  }
+  if (const char* why = track_tick_invalid(tt.weight, tt.margin, b->tr_width)) return fail(LLAMPC_E_ARG, "track tick: %s", why);
+  return LLAMPC_OK;
+}
+
+// llampc_plan (hp null), llampc_plan_corridor and (tt) llampc_plan_track: the blocking host-pointer tick.
 static int plan_blocking(llampc_bank* b, const llampc_plan_in* in, const double* hp, double weight,
-                         llampc_plan_out* out, double* err_out, double* wmean_out, double* cost_out) {
+                         llampc_plan_out* out, double* err_out, double* wmean_out, double* cost_out,
+                         const TrackTick* tt = nullptr) {
   if (!b || !out) return fail(LLAMPC_E_ARG, "bank/out is NULL");
   int rc;
   if (hp && in && (rc = check_corridor_mode(in))) return rc;   // E_ARG whatever else the bank lacks
+  // the track tick's refusals first, in their table's order, under the lock the launch is made under: the
+  // track and the outstanding async tick they are decided by cannot change in between
+  std::unique_lock<std::mutex> lk(b->mu, std::defer_lock);
+  if (tt) {
+    lk.lock();
+    if ((rc = check_track_tick(b, in, *tt))) return rc;
+  }
   if ((rc = check_plan_in(b, in))) return rc;
+  if (tt && in->H > LLAMPC_HMAX) return fail(LLAMPC_E_ARG, "H=%d above %d (the path state's horizon)", in->H, LLAMPC_HMAX);
   if (hp)                                // H is valid from here on
     if (const char* why = corridor_invalid(hp, in->H, weight)) return fail(LLAMPC_E_ARG, "corridor: %s", why);
-  std::lock_guard<std::mutex> lk(b->mu);
+  if (!lk.owns_lock()) lk.lock();
   bank_disarm(b);
   if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding: call llampc_plan_wait");
   DeviceGuard g(b->device);
@@ -541,7 +599,7 @@ static int plan_blocking(llampc_bank* b, const llampc_plan_in* in, const double*
   if (!err_out && !wmean_out && !cost_out && host_completion()) {
     // the record only: the kernel writes it to pinned host memory and publishes a tag
     uint64_t seq;
-    if ((rc = plan_launch_host(b, in, s, &seq, hp, weight)) || (rc = wait_host_tag(b, seq, out))) return rc;
+    if ((rc = plan_launch_host(b, in, s, &seq, hp, weight, tt)) || (rc = wait_host_tag(b, seq, out))) return rc;
     if (out->status) return status_fail(b, out->status);
     return LLAMPC_OK;
   }
@@ -555,7 +613,7 @@ static int plan_blocking(llampc_bank* b, const llampc_plan_in* in, const double*
   if ((rc = stage_inputs(b, in, &din, s, hp, &cor.hp))) return rc;
   if ((rc = plan_launch(b, din, b->d_out.get(), err_out ? b->d_err.get() : nullptr,
                         wmean_out ? b->d_wmean.get() : nullptr, d_cost, s, nullptr, 0, nullptr, nullptr, nullptr,
-                        hp ? &cor : nullptr)))
+                        hp ? &cor : nullptr, tt)))
     return rc;
   HIP_TRY(hipMemcpyAsync(b->h_out.get(), b->d_out.get(), sizeof(llampc_plan_out), hipMemcpyDeviceToHost, s));
   if (err_out && in->do_lookback)
@@ -581,6 +639,149 @@ int llampc_plan_corridor(llampc_bank* b, const llampc_plan_in* in, const double*
                          llampc_plan_out* out, double* err_out, double* wmean_out, double* cost_out) {
   if (!hp) return fail(LLAMPC_E_ARG, "hp is NULL (llampc_plan is the tick without a corridor)");
   return plan_blocking(b, in, hp, weight, out, err_out, wmean_out, cost_out);
+}
+
+int llampc_plan_track(llampc_bank* b, const llampc_plan_in* in, double weight, double margin, llampc_plan_out* out,
+                      double* err_out, double* wmean_out, double* cost_out) {
+  const TrackTick tt{weight, margin};
+  return plan_blocking(b, in, nullptr, 0.0, out, err_out, wmean_out, cost_out, &tt);
+}
+
+}  // extern "C"
+
+// The track tick's device state, allocated with the first track or path (the caller holds b->mu, the
+// bank's device is current): the path copies, their costs and the read-back, the flags, the tagged words.
+static int track_state(llampc_bank* b) {
+  if (b->d_trk) return LLAMPC_OK;
+  int rc;
+  if ((rc = b->d_trk.zalloc(4 * (size_t)kPlanPathStride + 2 + (size_t)kPlanTrackDbgDoubles, "track tick path state")) ||
+      (rc = b->d_trk_flags.zalloc(4, "track tick flags")) ||
+      (rc = b->d_hp_tag.zalloc(12 * (size_t)LLAMPC_HMAX, "track tick half-plane words")))
+    return rc;
+  return LLAMPC_OK;
+}
+
+extern "C" {
+
+int llampc_bank_set_track(llampc_bank* b, const double* centre, const double* theta, int32_t n, double track_length,
+                          double track_width) {
+  if (!b || !centre || !theta) return fail(LLAMPC_E_ARG, "NULL argument");
+  char why[128];
+  if (track_tables_invalid(centre, theta, n, track_length, track_width, why, sizeof why)) return fail(LLAMPC_E_ARG, "%s", why);
+  std::lock_guard<std::mutex> lk(b->mu);
+  bank_disarm(b);
+  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
+  DeviceGuard g(b->device);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // no launch reads the tables being replaced
+  b->tr_n = 0;
+  b->trk_path = track_path_next(b->trk_path, kPathClear);
+  b->trk_last_H = 0;
+  int rc;
+  if ((rc = track_state(b)) || (rc = b->d_track.reserve(3 * (size_t)n, 0, "track tables"))) return rc;
+  std::vector<double> h(3 * (size_t)n);
+  std::memcpy(h.data(), centre, 2 * (size_t)n * sizeof(double));
+  std::memcpy(h.data() + 2 * (size_t)n, theta, (size_t)n * sizeof(double));
+  HIP_TRY(hipMemcpy(b->d_track.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  b->tr_n = n;
+  b->tr_L = track_length;
+  b->tr_width = track_width;
+  return LLAMPC_OK;
+}
+
+int llampc_bank_set_path(llampc_bank* b, const double* path, int32_t H) {
+  if (!b) return fail(LLAMPC_E_ARG, "bank is NULL");
+  if (path) {
+    if (H < 1 || H > LLAMPC_HMAX) return fail(LLAMPC_E_ARG, "H=%d outside [1, %d]", H, LLAMPC_HMAX);
+    for (int i = 0; i < 2 * (H + 1); ++i)
+      if (!std::isfinite(path[i])) return fail(LLAMPC_E_ARG, "path: entry %d is not finite", i);
+  }
+  std::lock_guard<std::mutex> lk(b->mu);
+  bank_disarm(b);
+  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
+  if (!path) {
+    b->trk_path = track_path_next(b->trk_path, kPathClear);
+    return LLAMPC_OK;
+  }
+  DeviceGuard g(b->device);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // no launch reads or writes the copy being seeded
+  if (int rc = track_state(b)) return rc;
+  std::vector<double> h(2 * (size_t)kPlanPathStride, 0.0);
+  for (int r = 0; r < 2; ++r) std::memcpy(h.data() + (size_t)r * kPlanPathStride, path + (size_t)r * (H + 1), (H + 1) * sizeof(double));
+  const int32_t one = 1;
+  HIP_TRY(hipMemcpy(b->d_trk.get() + 2 * (size_t)kPlanPathStride * b->trk_cur, h.data(), h.size() * sizeof(double),
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_trk_flags.get() + b->trk_cur, &one, sizeof one, hipMemcpyHostToDevice));
+  b->trk_path = track_path_next(b->trk_path, kPathSeed, H);
+  return LLAMPC_OK;
+}
+
+int llampc_plan_track_async(llampc_bank* b, const llampc_plan_in* in, double weight, double margin) {
+  if (!b) return fail(LLAMPC_E_ARG, "bank is NULL");
+  const TrackTick tt{weight, margin};
+  std::lock_guard<std::mutex> lk(b->mu);
+  int rc;
+  if ((rc = check_track_tick(b, in, tt)) || (rc = check_plan_in(b, in))) return rc;
+  if (in->H > LLAMPC_HMAX) return fail(LLAMPC_E_ARG, "H=%d above %d (the path state's horizon)", in->H, LLAMPC_HMAX);
+  bank_disarm(b);
+  DeviceGuard g(b->device);
+  hipStream_t s = b->stream;
+  if (host_completion()) {
+    uint64_t seq;
+    if ((rc = plan_launch_host(b, in, s, &seq, nullptr, 0.0, &tt))) return rc;
+    b->async_seq = seq;
+  } else {
+    llampc_plan_in din;
+    if ((rc = stage_inputs(b, in, &din, s))) return rc;
+    b->async_seq = 0;
+    if ((rc = plan_launch(b, din, b->d_out.get(), nullptr, nullptr, nullptr, s, nullptr, 0, nullptr, nullptr, nullptr,
+                          nullptr, &tt)))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(b->h_out.get(), b->d_out.get(), sizeof(llampc_plan_out), hipMemcpyDeviceToHost, s));
+  }
+  b->async_pending = true;
+  return LLAMPC_OK;
+}
+
+int llampc_bank_track_corridor(llampc_bank* b, double* path, double* hp, double* theta, int32_t* valid,
+                               double* next_path, int32_t* next_valid, double* next_cost) {
+  if (!b || !path || !hp || !theta || !valid || !next_path || !next_valid || !next_cost)
+    return fail(LLAMPC_E_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(b->mu);
+  if (!b->trk_last_H) return fail(LLAMPC_E_STATE, "the bank's last launch was not a track tick");
+  DeviceGuard g(b->device);
+  HIP_TRY(hipStreamSynchronize(b->stream));      // the launch's end: the path update follows the record
+  const int H = b->trk_last_H;
+  const size_t ps = 2 * (size_t)kPlanPathStride;
+  std::vector<double> h(2 * ps + 2 + (size_t)kPlanTrackDbgDoubles);
+  int32_t fl[4];
+  HIP_TRY(hipMemcpy(h.data(), b->d_trk.get(), h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(fl, b->d_trk_flags.get(), sizeof fl, hipMemcpyDeviceToHost));
+  const int cur = b->trk_cur;            // the copy the tick wrote
+  const double* dbg = h.data() + 2 * ps + 2;
+  for (int r = 0; r < 2; ++r) {
+    std::memcpy(path + (size_t)r * (H + 1), dbg + (size_t)r * kPlanPathStride, (H + 1) * sizeof(double));
+    std::memcpy(next_path + (size_t)r * (H + 1), h.data() + ps * cur + (size_t)r * kPlanPathStride, (H + 1) * sizeof(double));
+  }
+  std::memcpy(hp, dbg + ps, 6 * (size_t)H * sizeof(double));
+  std::memcpy(theta, dbg + ps + 6 * LLAMPC_HMAX, (size_t)H * sizeof(double));
+  *valid = fl[2];
+  *next_valid = fl[cur];
+  *next_cost = h[2 * ps + cur];
+  return LLAMPC_OK;
+}
+
+int llampc_plan_variant_track(int64_t n, int32_t C, int32_t H, int32_t share, int32_t track_n, int32_t out[5]) {
+  if (!out) return fail(LLAMPC_E_ARG, "NULL argument");
+  if (n < 1 || C < 1 || H < 1 || H > LLAMPC_HMAX || track_n < 2 || track_n > kTrackMaxPoints)
+    return fail(LLAMPC_E_ARG, "n %lld, C %d, H %d (<= %d), track_n %d (2..%d)", (long long)n, C, H, LLAMPC_HMAX, track_n,
+                kTrackMaxPoints);
+  const PlanShape s = lookahead_shape(n, true, C, H, LLAMPC_RK4, LLAMPC_XREF_GIVEN, share, false, false, track_n);
+  out[0] = s.lpm;
+  out[1] = s.G;
+  out[2] = s.cpl;
+  out[3] = s.stage ? 1 : 0;
+  out[4] = s.nb_cor;
+  return LLAMPC_OK;
 }
 
 int llampc_bank_set_raceline(llampc_bank* b, const double* knots, int32_t n, const double* xy,

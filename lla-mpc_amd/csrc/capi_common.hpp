@@ -198,6 +198,21 @@ struct llampc_bank {
   // the controller whose armed launch waits on this bank's stream (llampc_ctl_set_prelaunch):
   // every other call that enqueues on the stream cancels it first (bank_disarm)
   llampc_ctl* armed = nullptr;
+  // the track tick (llampc_plan_track; kernels.hpp PlanTrack)
+  DevBuf<double> d_track;                // llampc_bank_set_track: cx | cy | tt, [3][tr_n]
+  int32_t tr_n = 0;                      // 0: no track set
+  double tr_L = 0.0, tr_width = 0.0;
+  DevBuf<double> d_trk;                  // the path copies [2][2][HMAX + 1] | their costs [2] | the read-back
+  DevBuf<int32_t> d_trk_flags;           // the copies' valid flags [2] | the read-back's | the late word
+  DevBuf<uint64_t> d_hp_tag;             // [12 HMAX] tagged half-plane words
+  uint32_t tseq = 0;                     // the half-plane words' own sequence: every track tick advances it
+  int32_t trk_cur = 0;                   // the copy that holds (or will hold, once the stream drains) the newest path
+  llampc::TrackPathState trk_path{0};    // the host's half of the path rule
+  int32_t trk_last_H = 0;                // the horizon of the last launch if it was a track tick, else 0
+};
+// A track tick's own arguments beside the plan input.
+struct TrackTick {
+  double weight, margin;
 };
 static inline llampc::BankView bank_view(const llampc_bank& b) {
   return {b.d_params.get(), b.n, b.goff, b.veh, b.d_ring.get(), b.W, b.slot, b.d_wmean.get(),
@@ -213,11 +228,13 @@ int bank_dedicate(llampc_bank* b);
 int check_plan_in(const llampc_bank* b, const llampc_plan_in* in);
 // The tick on device pointers: ONE launch (look-back + look-ahead + completion).  host_tag:
 // host completion; pk: the inputs as kernel arguments; px: the fused peer exchange; cor: the
-// look-ahead's corridor (device half-planes and weight; never with pk or px).
+// look-ahead's corridor (device half-planes and weight; never with pk or px); tt: the track tick (the
+// corridor built in the launch from the bank's track and path state; never with pk, px or cor).
 int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out, double* d_err, double* d_wmean,
                 double* d_cost, hipStream_t s, uint64_t* host_tag = nullptr, uint64_t host_seq = 0,
                 const llampc::InlinePack* pk = nullptr, llampc_mailbox* px = nullptr,
-                llampc_plan_out* px_merged = nullptr, const llampc::PlanCorridor* cor = nullptr);
+                llampc_plan_out* px_merged = nullptr, const llampc::PlanCorridor* cor = nullptr,
+                const TrackTick* tt = nullptr);
 inline hipStream_t pick_stream(llampc_bank* b, void* s) { return s ? (hipStream_t)s : b->stream; }
 
 // llampc_nlp_create's checks of a cfg (capi_nlp.hip), llampc_nlp_batch_create's too.

@@ -86,6 +86,32 @@ inline const char* track_tables_invalid(const double* centre, const double* thet
   return nullptr;
 }
 
+// The host's half of the track tick's path rule (llampc_plan_track; kernels.hpp PlanTrack): the path
+// state on the device is offered to a track tick only when its horizon is the tick's, and it was
+// written by the bank's immediately preceding launch, itself a track tick, or seeded by
+// llampc_bank_set_path since.  Any other launch on the bank, llampc_bank_reset, llampc_bank_set_track
+// and llampc_bank_set_path(NULL) clear it.  H = 0: nothing on offer.
+struct TrackPathState {
+  int32_t H;
+};
+enum TrackPathEvent {
+  kPathTrackTick,                        // a track tick of horizon H was enqueued: it writes the next path
+  kPathSeed,                             // llampc_bank_set_path(P, H)
+  kPathOtherLaunch,                      // any other plan launch on the bank
+  kPathClear,                            // llampc_bank_reset, llampc_bank_set_track, llampc_bank_set_path(NULL)
+};
+inline TrackPathState track_path_next(TrackPathState, TrackPathEvent ev, int32_t H = 0) {
+  return TrackPathState{(ev == kPathTrackTick || ev == kPathSeed) ? H : 0};
+}
+inline bool track_path_offered(TrackPathState s, int32_t H) { return s.H != 0 && s.H == H; }
+
+// The track tick's weight and margin as llampc_plan_track accepts them: null if valid.
+inline const char* track_tick_invalid(double weight, double margin, double track_width) {
+  if (!(weight >= 0) || !std::isfinite(weight)) return "weight must be finite and >= 0";
+  if (!std::isfinite(margin) || !(track_width / 2 - margin > 0)) return "margin must be finite and below track_width / 2";
+  return nullptr;
+}
+
 // A corridor hp [H][6] (llampc_nlp_solve_corridor: per step (a0, a1, b, c0, c1, d), a.p <= b and
 // c.p <= d) and its weight as the solve accepts them: finite normals, offsets finite or +inf (the
 // disabled half-plane's), a finite weight >= 0.  Null if valid, else what is wrong.

@@ -291,8 +291,10 @@ static void with_variant(int integ, int lpm, F&& f) {
 }
 
 hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, FinalLaunch f,
-                       hipStream_t s, const InlinePack* pk, int32_t share, const PlanCorridor* cor) {
+                       hipStream_t s, const InlinePack* pk, int32_t share, const PlanCorridor* cor,
+                       const PlanTrack* trk) {
   if (cor && !cor->hp) return hipErrorInvalidValue;
+  if (trk && (trk->trk.n < 2 || trk->trk.n > kTrackMaxPoints || !trk->hp_tag)) return hipErrorInvalidValue;
   // 1. the launch's shape (launch_shape.hpp): the one place that decides it, or refuses
   PlanShapeIn in{};
   in.n = lb ? lb->n : la ? la->n : 0;
@@ -315,6 +317,7 @@ hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, Fina
   in.px_G = f.px_G;
   in.pack = pk != nullptr;
   in.corridor = cor != nullptr;
+  in.track_n = trk ? trk->trk.n : 0;
   const PlanShape sh = plan_shape(in, device_cus());
   if (sh.refuse) return hipErrorInvalidValue;
   // 2. what the kernels read of it
@@ -333,7 +336,9 @@ hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, Fina
   f.do_lb = lb != nullptr;
   f.do_la = la != nullptr;
   // 3. the variant group's launcher
-  if (sh.integ == LLAMPC_RK6) {
+  if (trk) {
+    launch_plan_track(lbv, lav, f, sh.G, sh.cpl, sh.stage, sh.lpm, sh.lds, s, *trk);
+  } else if (sh.integ == LLAMPC_RK6) {
     launch_plan_group<2, 1>(lbv, lav, f, sh.G, sh.cpl, sh.stage, sh.lds, s, 0);
   } else {
     with_variant(sh.integ, sh.lpm, [&](auto I, auto L) {

@@ -131,6 +131,48 @@ struct PlanCorridor {
   double weight;
 };
 
+// The track tick (llampc_plan_track; plan_track_rk4.hip plan_kernel_track): the corridor tick whose
+// half-planes H corridor blocks of the same launch build from the bank's track along the bank's path
+// state — plan_kernel_track's own trailing argument, so the launch structs above keep their layout.
+//   path state   the NEXT tick's path P [2][HMAX + 1] (P_j = X[ctl_path_index(j, H)] of a tick's chosen
+//                (sel_model, sel_cand) rollout, constraints.default_path's prev_xmpc rule), its cost and
+//                a valid flag (cost and positions finite, sel_owned, 0 <= sel_cand < C).  Two copies by
+//                launch parity: a tick's corridor blocks read one while its completing block writes the
+//                other, so a corridor block that starts late never reads a half-written path (ctl.hpp).
+//   path_ok      the host's half of the validity rule (capi_host.hpp track_path_offered).  Invalid: every
+//                row is constraints.disabled's (0, 0, +inf, 0, 0, +inf).
+//   hp_tag       [12 H] tagged words, the halves (hi, lo) of row k - 1's six values from 12 (k - 1) on:
+//                corridor block k publishes them, every look-ahead block and the completing block poll
+//                them.  Tagged with `seq`, a sequence of the track ticks' own: the launch's tag
+//                (LookaheadLaunch::seq) advances on polled ticks only, so a tick without a look-back would
+//                accept the rows of the tick before.
+//   dbg          what llampc_bank_track_corridor reads back once the stream has drained: P [2][HMAX + 1] |
+//                hp [HMAX][6] | theta [HMAX], and the path's validity in dbg_valid.
+//   late         a look-ahead block whose wait for a half-plane word ran out (poll x 2^16 ticks of
+//                s_memrealtime; never expected) stores seq here: the record's status then reads
+//                LLAMPC_STATUS_POLL_TIMEOUT.
+constexpr int kPlanPathStride = LLAMPC_HMAX + 1;
+constexpr int kPlanTrackDbgDoubles = 2 * kPlanPathStride + 7 * LLAMPC_HMAX;
+struct PlanTrack {
+  TrackK trk;
+  double hw, weight;                     // track_width / 2 - margin; the corridor term's weight
+  uint64_t* hp_tag;
+  const double* path_rd;
+  double* path_wr;
+  const int32_t* valid_rd;
+  int32_t* valid_wr;
+  double* cost_wr;                       // the re-run's cost (the read-back's next_cost)
+  double* dbg;
+  int32_t* dbg_valid;
+  uint32_t* late;
+  uint32_t seq, poll;
+  int32_t path_ok, pad;
+};
+// plan_kernel_track<stage, lpm> (plan_track_rk4.hip): RK4, the shared xref, device inputs; the grid is
+// f.nb_lb + la.H + f.nb_la blocks.
+void launch_plan_track(const LookbackLaunch& lb, const LookaheadLaunch& la, const FinalLaunch& f, int G, int cpl,
+                       bool stage, int lpm, size_t lds, hipStream_t s, const PlanTrack& trk);
+
 // The whole tick in ONE launch: look-back blocks (if lb), look-ahead blocks (if la), and
 // the completion stages run by ticket winners; writes f.out.  f.nb_* / f.do_*, the look-back's R
 // and the raceline's wcap are set here, from the launch's shape (launch_shape.hpp plan_shape: the
@@ -141,9 +183,11 @@ struct PlanCorridor {
 // cor != null: the corridor launch (plan_kernel_corr) — block per models on the unsplit rollouts,
 // never the work queue, the inline pack or the fused peer exchange; refused for RK6, the raceline
 // reference, pk or a peer exchange (f.px_G).
+// trk != null: the track tick (plan_kernel_track) — the corridor launch with H corridor blocks between
+// the look-back's and the look-ahead's; refused as the corridor launch is and for NLP-Euler; never with cor.
 hipError_t launch_plan(const LookbackLaunch* lb, const LookaheadLaunch* la, FinalLaunch f,
                        hipStream_t s, const InlinePack* pk = nullptr, int32_t share = 1,
-                       const PlanCorridor* cor = nullptr);
+                       const PlanCorridor* cor = nullptr, const PlanTrack* trk = nullptr);
 // The plan-kernel variant groups (plan_dev.hpp; one translation unit per group, plan_*.hip):
 // (integrator, lanes per rollout) with the staged / unstaged inputs and, for RK4 at LPM 1, the
 // work-queue layouts; the inline-pack host ticks per LPM.  lds: plan_shape's, every floor applied.

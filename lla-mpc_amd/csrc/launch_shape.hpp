@@ -128,6 +128,15 @@ inline size_t lb_final_lds_bytes(int nb_lb, int32_t K) {
                   kScratchBytes + (size_t)kWaves * kRankBytes + kBlockMergeBytes);
 }
 
+// The track tick's LDS besides the look-ahead's: a corridor block's two reduction rows and the centre
+// line's three tables (corridor_block_dev.hpp), and the completing block's re-run of the chosen rollout
+// (plan_track_dev.hpp): xref [H+1][2] | one candidate's staged inputs [H][kStageW] | hp [H][6] | the
+// positions [2][H+1] | x_t [6] | the cost, its flag and the record's selection (64 B).
+inline size_t track_block_lds_bytes(int32_t track_n) { return 64 + 24 * (size_t)track_n; }
+inline size_t track_rerun_lds_bytes(int32_t H) {
+  return kScratchBytes + 16 * (size_t)(H + 1) + 8 * kStageW * (size_t)H + 48 * (size_t)H + 16 * (size_t)(H + 1) + 48 + 64;
+}
+
 // What a plan launch is asked for (launch_plan builds it from its arguments, cus from the device).
 struct PlanShapeIn {
   int64_t n;                             // the bank's models
@@ -140,11 +149,12 @@ struct PlanShapeIn {
   int32_t px_G;                          // the fused peer exchange's world (0: none)
   bool pack, corridor;                   // the inputs come as an InlinePack; a PlanCorridor rides along
   bool wq_counter;                       // the bank has a work-queue unit counter
+  int32_t track_n;                       // the track tick: the centre line's points (0: none); a PlanTrack rides along
 };
 
 // The plan kernels by their trailing argument (plan_dev.hpp): plan_kernel, plan_kernel_inl (the
-// InlinePack), plan_kernel_corr (the PlanCorridor).
-enum PlanFamily { kPlanPlain = 0, kPlanInline = 1, kPlanCorridor = 2 };
+// InlinePack), plan_kernel_corr (the PlanCorridor), plan_kernel_track (the PlanTrack; plan_track_dev.hpp).
+enum PlanFamily { kPlanPlain = 0, kPlanInline = 1, kPlanCorridor = 2, kPlanTrack = 3 };
 
 // Why plan_shape refuses a launch (PlanShape::refuse points at one of these).  The corridor's
 // three mode refusals are the C ABI's messages (capi.hip check_corridor_mode).
@@ -153,6 +163,14 @@ inline constexpr char kNoCorridorRk6[] = "the corridor look-ahead has no RK6 rol
 inline constexpr char kNoCorridorRaceline[] =
     "the corridor look-ahead takes the given xref only (not LLAMPC_XREF_RACELINE)";
 inline constexpr char kNoCorridorInputs[] = "the corridor launch takes device inputs and no fused peer exchange";
+// The track tick's refusals (capi.hip check_track_tick passes the mode ones on).
+inline constexpr char kNoTrackLookahead[] = "the track tick's corridor belongs to the look-ahead: do_lookahead is 0";
+inline constexpr char kNoTrackRk6[] = "the track tick has no RK6 rollout";
+inline constexpr char kNoTrackEuler[] = "the track tick has no NLP-Euler rollout (llampc_plan_corridor takes host-built rows)";
+inline constexpr char kNoTrackRaceline[] = "the track tick takes the given xref only (not LLAMPC_XREF_RACELINE)";
+inline constexpr char kNoTrackPack[] = "the track tick takes device inputs (no inline pack)";
+inline constexpr char kNoTrackPeer[] = "the track tick has no fused peer exchange";
+inline constexpr char kNoTrackCorridor[] = "the track tick builds its own corridor (no PlanCorridor beside it)";
 inline constexpr char kNoIntegrator[] = "unknown integrator";
 inline constexpr char kNoWork[] = "nothing to launch: no look-back and no look-ahead block";
 inline constexpr char kNoPeer[] = "the fused peer exchange: RK4, the given xref, device inputs, at most kPeerFuseMax ranks";
@@ -167,6 +185,7 @@ struct PlanShape {
   int wq;                                // work-queue layout (kernels.hpp wq_threads): 0, 1 or 2
   bool px, xm;                           // the fused peer exchange; the per-model raceline reference
   int R, nb_lb, nb_la, threads;          // models per look-back lane, the block counts, threads per block
+  int nb_cor;                            // the track tick's corridor blocks (H), between the look-back's and the look-ahead's
   size_t lds;                            // the launch's dynamic LDS, every floor applied
   int32_t wcap;                          // the raceline's speed window, in segments
   const char* refuse;
@@ -176,7 +195,7 @@ struct PlanShape {
 // LLAMPC_NO_WQ and LLAMPC_WQ_WAVES are read on every call, LLAMPC_LB_R once per process.
 inline PlanShape plan_shape(const PlanShapeIn& in, int cus) {
   PlanShape s{};
-  s.family = in.corridor ? kPlanCorridor : in.pack ? kPlanInline : kPlanPlain;
+  s.family = in.track_n > 0 ? kPlanTrack : in.corridor ? kPlanCorridor : in.pack ? kPlanInline : kPlanPlain;
   s.integ = in.la ? in.integrator : LLAMPC_RK4;
   s.lpm = s.G = s.cpl = 1;
   s.threads = kBlock;
@@ -188,6 +207,15 @@ inline PlanShape plan_shape(const PlanShapeIn& in, int cus) {
   };
   // what the modes refuse, before any size is worked out.  The corridor launch: RK4 or NLP-Euler
   // on the shared xref, device inputs, no peer exchange
+  if (in.track_n > 0) {
+    if (!in.la) return no(kNoTrackLookahead);
+    if (in.integrator == LLAMPC_RK6) return no(kNoTrackRk6);
+    if (in.integrator == LLAMPC_EULER_NLP) return no(kNoTrackEuler);
+    if (in.xref_mode != LLAMPC_XREF_GIVEN) return no(kNoTrackRaceline);
+    if (in.pack) return no(kNoTrackPack);
+    if (in.px_G) return no(kNoTrackPeer);
+    if (in.corridor) return no(kNoTrackCorridor);
+  }
   if (in.corridor) {
     if (!in.la) return no(kNoCorridorLookahead);
     if (in.integrator == LLAMPC_RK6) return no(kNoCorridorRk6);
@@ -225,10 +253,16 @@ inline PlanShape plan_shape(const PlanShapeIn& in, int cus) {
       s.wcap = (int32_t)std::min<size_t>(room / per_seg, (size_t)(in.rl_n - 1));
       lds = std::max(lds, base + rl + per_seg * (size_t)s.wcap);
     } else {
-      lds = std::max(lds, lookahead_lds_bytes(in.C, in.H, &s.stage, in.corridor ? 48 * (size_t)in.H : 0));
+      lds = std::max(lds, lookahead_lds_bytes(in.C, in.H, &s.stage, in.corridor || in.track_n > 0 ? 48 * (size_t)in.H : 0));
     }
   }
   if (s.nb_lb + s.nb_la == 0) return no(kNoWork);
+  // The track tick: H corridor blocks, each with the centre line's tables in LDS (corridor_block_dev.hpp),
+  // and the completing block's re-run of the chosen rollout (plan_track_dev.hpp track_rerun_lds_bytes)
+  if (in.track_n > 0) {
+    s.nb_cor = in.H;
+    lds = std::max(lds, std::max(track_block_lds_bytes(in.track_n), track_rerun_lds_bytes(in.H)));
+  }
   // Work queue (the throughput regime): LPM 1 with a model inside one wave (G <= 64), RK4 on
   // the shared xref, device inputs, at least 1.75 rounds of look-ahead blocks per CU — then one
   // block per CU (minus the completing look-back block's) takes units of models from the
@@ -241,7 +275,8 @@ inline PlanShape plan_shape(const PlanShapeIn& in, int cus) {
   // waits for those slow units.  LLAMPC_NO_WQ=1 keeps the block-per-models layout,
   // LLAMPC_WQ_WAVES=4|8 forces a work-queue block size (A/B runs).
   if (in.la && in.wq_counter && s.lpm == 1 && s.G <= 64 && s.integ == LLAMPC_RK4 &&
-      in.xref_mode == LLAMPC_XREF_GIVEN && !in.pack && !in.corridor && getenv("LLAMPC_NO_WQ") == nullptr) {
+      in.xref_mode == LLAMPC_XREF_GIVEN && !in.pack && !in.corridor && in.track_n <= 0 &&
+      getenv("LLAMPC_NO_WQ") == nullptr) {
     const int nw = std::max(1, cus - 1);
     const char* force = getenv("LLAMPC_WQ_WAVES");
     const int forced = force ? atoi(force) : 0;

@@ -66,6 +66,10 @@ __device__ __forceinline__ void la_publish(const LookaheadLaunch& a, int blk, co
 // bank's work counter, so the staging prologue runs once per CU instead of once per 4 models
 // and no CU waits for a new block between units (v29 stamps at C = 64: prologue 3.4 us and
 // reduction 2 us of each 45 us block).
+// (The track tick's look-ahead block, plan_track_dev.hpp track_lookahead_block, restates this function's
+// kBatch / CORR path — prologue, stage_write, pin_consts, model_setup, rollouts, publication — with a poll
+// of tagged words where this one loads ghp; tests/test_plan_track_gpu.py holds the two bitwise equal.  A
+// change to that path here belongs there too.)
 // CORR (the corridor look-ahead, plan_kernel_corr): the half-planes ghp [H][6] (global) are copied
 // to LDS behind the staged inputs — loaded with the prologue's other inputs, stored ahead of its
 // barrier — and every rollout adds cw times its summed squared slacks (rollout_dev.hpp kRCorr) on the

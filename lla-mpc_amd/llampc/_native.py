@@ -140,6 +140,19 @@ _SIGNATURES = {
     # bank, in, hp [H][6], weight, then llampc_plan's outputs
     "llampc_plan_corridor": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), _dp, C.c_double, C.POINTER(PlanOut),
                                        _dp, _dp, _dp]),
+    # the track tick: centre [2][n], theta [n], n, track_length, track_width
+    "llampc_bank_set_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double]),
+    # path [2][H+1] or NULL, H
+    "llampc_bank_set_path": (C.c_int, [C.c_void_p, _dp, C.c_int32]),
+    # bank, in, weight, margin, then llampc_plan's outputs
+    "llampc_plan_track": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), C.c_double, C.c_double, C.POINTER(PlanOut),
+                                    _dp, _dp, _dp]),
+    "llampc_plan_track_async": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), C.c_double, C.c_double]),
+    # -> path [2][H+1], hp [H][6], theta [H], valid, next_path [2][H+1], next_valid, next_cost
+    "llampc_bank_track_corridor": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.POINTER(C.c_int32), _dp,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "llampc_plan_variant_track": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.POINTER(C.c_int32)]),
     "llampc_plan_device": (C.c_int, [C.c_void_p, C.POINTER(PlanIn), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "llampc_merge": (C.c_int, [C.POINTER(PlanOut), C.c_int32, C.c_int32, C.POINTER(PlanOut)]),
@@ -294,6 +307,14 @@ def plan_variant_corridor(n: int, C_: int, H: int, integrator="rk4", share: int 
     integ = INTEGRATORS[integrator] if isinstance(integrator, str) else int(integrator)
     check(load().llampc_plan_variant_corridor(int(n), int(C_), int(H), integ, int(share), out))
     return dict(lpm=out[0], G=out[1], cpl=out[2], stage=bool(out[3]))
+
+
+def plan_variant_track(n: int, C_: int, H: int, track_n: int, share: int = 1) -> dict:
+    """The variant a track tick takes (llampc_plan_variant_track; host only, reads LLAMPC_LPM as the
+    launch does): {lpm, G, cpl, stage, nb_cor}, nb_cor the corridor blocks (H)."""
+    out = (C.c_int32 * 5)()
+    check(load().llampc_plan_variant_track(int(n), int(C_), int(H), int(share), int(track_n), out))
+    return dict(lpm=out[0], G=out[1], cpl=out[2], stage=bool(out[3]), nb_cor=out[4])
 
 
 CTL_VARIANT_FIELDS = ("lpm", "G", "cpl", "mpb", "s4", "zfit", "R", "nb_lb", "nb_la")

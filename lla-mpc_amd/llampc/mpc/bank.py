@@ -81,8 +81,38 @@ def check_corridor(corridor, weight, H, integrator="rk4", raceline_start=None):
     return hp, weight
 
 
+def check_track_tick(track, weight, margin, integrator="rk4", raceline_start=None, do_lookahead=True,
+                     corridor=None):
+    """A track tick's arguments as the library takes them (llampc_plan_track): -> (weight, margin),
+    checked before the library is touched.  ValueError: no track set on the bank, ``corridor`` given
+    as well, no look-ahead, an integrator other than "rk4", raceline_start (the per-model reference),
+    a weight negative or non-finite (check_corridor's rule), a margin that leaves no corridor
+    (constraints.require_margin)."""
+    from llampc.mpc import constraints
+    if corridor is not None:
+        raise ValueError("corridor and track_corridor cannot be combined: the track tick builds its own rows")
+    if track is None:
+        raise ValueError("track_corridor=True needs ModelBank.set_track(track) first")
+    if not do_lookahead:
+        raise ValueError("track_corridor=True: the corridor belongs to the look-ahead (do_lookahead is off)")
+    if integrator != "rk4":
+        raise ValueError(f"the track tick has no {integrator} rollout: integrator must be 'rk4'")
+    if raceline_start is not None:
+        raise ValueError("track_corridor and raceline_start cannot be combined: the track tick takes the shared xref")
+    weight = float(weight)
+    if not (np.isfinite(weight) and weight >= 0):
+        raise ValueError("corridor_weight must be finite and >= 0")
+    margin = float(margin)
+    if not np.isfinite(margin):
+        raise ValueError(f"corridor_margin {margin} is not finite")
+    constraints.require_margin(track, margin)
+    return weight, margin
+
+
 class ModelBank:
     """A shard of the model bank resident on one HIP device."""
+    track = None                         # set_track's track (the track tick's)
+    _track_H = None                      # the horizon of the last track tick made through this object
 
     def __init__(self, params6, shared: dict | None = None, W: int = 10, device: int = 0,
                  global_offset: int = 0, input_acc: bool = False, approx: bool = False):
@@ -241,6 +271,48 @@ class ModelBank:
                                                       nat.dptr(speed), nat.dptr(mus), len(mus)))
         self.raceline = track
 
+    def set_track(self, track):
+        """Attach ``track`` (center_line, theta_track, track_length, track_width) for
+        ``plan_raw(track_corridor=True)`` ticks (llampc_bank_set_track).  Invalidates the path."""
+        from llampc.mpc import constraints
+        constraints.require_track(track, "ModelBank.set_track")
+        centre, theta, length, width = constraints.track_tables(track)
+        nat.check(nat.load().llampc_bank_set_track(self.handle, centre.ctypes.data, theta.ctypes.data,
+                                                   centre.shape[1], length, width))
+        self.track = track
+
+    def set_corridor_path(self, P):
+        """Seed the next track tick's path P [2, H+1] (row k of its corridor is built at P[:, k]), or
+        with None invalidate it (llampc_bank_set_path)."""
+        if P is None:
+            nat.check(nat.load().llampc_bank_set_path(self.handle, None, 0))
+            return
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if P.ndim != 2 or P.shape[0] != 2 or P.shape[1] < 2:
+            raise ValueError(f"path must be [2, H+1], got {P.shape}")
+        nat.check(nat.load().llampc_bank_set_path(self.handle, nat.dptr(P), P.shape[1] - 1))
+
+    def track_corridor(self) -> dict:
+        """The last track tick's read-back (llampc_bank_track_corridor), H that tick's horizon: path
+        [2, H+1] the tick built its corridor along (NaN without a valid one), hp [H, 6], theta [H],
+        valid, and what it left for the next tick: next_path [2, H+1], next_valid, next_cost.
+        NativeError (E_STATE) unless the bank's last launch was a track tick.  The library writes by
+        the horizon it remembers, so the buffers are sized for the largest one (LLAMPC_HMAX) and cut
+        to the horizon of the last track tick made through this object."""
+        path, nxt = np.empty(2 * (nat.HMAX + 1)), np.empty(2 * (nat.HMAX + 1))
+        hp, theta = np.empty(6 * nat.HMAX), np.empty(nat.HMAX)
+        valid, nvalid, ncost = nat.C.c_int32(), nat.C.c_int32(), nat.C.c_double()
+        nat.check(nat.load().llampc_bank_track_corridor(self.handle, nat.dptr(path), nat.dptr(hp), nat.dptr(theta),
+                                                        nat.C.byref(valid), nat.dptr(nxt), nat.C.byref(nvalid),
+                                                        nat.C.byref(ncost)))
+        H = self._track_H
+        if H is None:
+            raise nat.NativeError("the last track tick was not made through this ModelBank: its horizon is unknown")
+        return dict(path=path[:2 * (H + 1)].reshape(2, H + 1).copy(), hp=hp[:6 * H].reshape(H, 6).copy(),
+                    theta=theta[:H].copy(), valid=bool(valid.value),
+                    next_path=nxt[:2 * (H + 1)].reshape(2, H + 1).copy(), next_valid=bool(nvalid.value),
+                    next_cost=ncost.value)
+
     def _plan_in(self, x_prev, u_prev, x_now, U, xref, uprev, Ts, K, integrator, do_lookback,
                  do_lookahead, current_model, nan_policy, cost, raceline_start=None):
         """raceline_start = (s0, v0, scale): xref_mode RACELINE (xref is then unused)."""
@@ -286,11 +358,18 @@ class ModelBank:
     def plan_raw(self, x_prev, u_prev, x_now, U, xref, uprev, Ts=0.02, K=10, integrator="rk4",
                  do_lookback=True, do_lookahead=True, current_model=0, nan_policy=nat.NAN_FIRST,
                  cost=None, return_errors=False, return_window_mean=False, return_costs=False,
-                 raceline_start=None, corridor=None, corridor_weight=1e4):
+                 raceline_start=None, corridor=None, corridor_weight=1e4, track_corridor=False,
+                 corridor_margin=0.0):
         """The fused tick (llampc_plan): returns (PlanOut, errors, window_mean, costs).
         corridor: None, or hp [H, 6] as in lookahead() — the look-ahead half under the corridor
-        (llampc_plan_corridor), everything else of the tick unchanged."""
-        if corridor is not None:
+        (llampc_plan_corridor), everything else of the tick unchanged.
+        track_corridor=True: the corridor built inside the launch from set_track's track, along the
+        previous track tick's chosen rollout (llampc_plan_track; corridor_margin narrows it); the
+        host builds no geometry and moves no path between ticks."""
+        if track_corridor:
+            corridor_weight, corridor_margin = check_track_tick(self.track, corridor_weight, corridor_margin, integrator,
+                                                                raceline_start, do_lookahead, corridor)
+        elif corridor is not None:
             Ush = np.shape(U)
             corridor, corridor_weight = check_corridor(corridor, corridor_weight, Ush[-2] if len(Ush) >= 2 else -1,
                                                        integrator, raceline_start)
@@ -302,7 +381,11 @@ class ModelBank:
         wm = np.empty(self.n) if return_window_mean else None
         costs = np.empty((self.n, C_)) if return_costs else None
         out = nat.PlanOut()
-        if corridor is None:
+        if track_corridor:
+            nat.check(nat.load().llampc_plan_track(self.handle, nat.C.byref(pin), corridor_weight, corridor_margin,
+                                                   nat.C.byref(out), nat.dptr(err), nat.dptr(wm), nat.dptr(costs)))
+            self._track_H = int(pin.H)
+        elif corridor is None:
             nat.check(nat.load().llampc_plan(self.handle, nat.C.byref(pin), nat.C.byref(out), nat.dptr(err),
                                              nat.dptr(wm), nat.dptr(costs)))
         else:
@@ -313,14 +396,22 @@ class ModelBank:
 
     def plan_async(self, x_prev, u_prev, x_now, U, xref, uprev, Ts=0.02, K=10, integrator="rk4",
                    do_lookback=True, do_lookahead=True, current_model=0, nan_policy=nat.NAN_FIRST,
-                   cost=None, raceline_start=None):
+                   cost=None, raceline_start=None, track_corridor=False, corridor_weight=1e4, corridor_margin=0.0):
         """Enqueue one tick (llampc_plan_async): inputs are staged before return, the tick
         runs on the bank's stream; ``plan_wait()`` returns its PlanOut.  Independent banks
-        (e.g. one per track) overlap on the device."""
+        (e.g. one per track) overlap on the device.  track_corridor=True: the track tick
+        (llampc_plan_track_async), as in plan_raw."""
+        if track_corridor:
+            corridor_weight, corridor_margin = check_track_tick(self.track, corridor_weight, corridor_margin, integrator,
+                                                                raceline_start, do_lookahead)
         pin, keep = self._plan_in(x_prev, u_prev, x_now, U, xref, uprev, Ts, K, integrator,
                                   do_lookback, do_lookahead, current_model, nan_policy, cost,
                                   raceline_start)
-        nat.check(nat.load().llampc_plan_async(self.handle, nat.C.byref(pin)))
+        if track_corridor:
+            nat.check(nat.load().llampc_plan_track_async(self.handle, nat.C.byref(pin), corridor_weight, corridor_margin))
+            self._track_H = int(pin.H)
+        else:
+            nat.check(nat.load().llampc_plan_async(self.handle, nat.C.byref(pin)))
 
     def plan_wait(self):
         out = nat.PlanOut()

@@ -67,7 +67,8 @@ def result_from_out(o: nat.PlanOut, U=None, **extra) -> PlanResult:
 def plan(bank: ModelBank, x_t, u_prev, x_prev, xref, U_cand, uprev=None, Ts=0.02, K=10,
          current_model=0, integrator="rk4", cost=None, nan_policy=nat.NAN_FIRST,
          do_lookback=True, return_errors=False, return_window_mean=False,
-         return_costs=False, raceline_start=None, corridor=None, corridor_weight=1e4) -> PlanResult:
+         return_costs=False, raceline_start=None, corridor=None, corridor_weight=1e4,
+         track_corridor=False, corridor_margin=0.0) -> PlanResult:
     """One tick.  x_t [6]; (x_prev [6], u_prev [2]) the previous transition (pass
     do_lookback=False on the first tick, rt.py:347); xref [2, H+1]; U_cand [C, H, 2];
     uprev [2] is the input applied last (defaults to u_prev), used for du_0
@@ -77,7 +78,12 @@ def plan(bank: ModelBank, x_t, u_prev, x_prev, xref, U_cand, uprev=None, Ts=0.02
     corridor = hp [H, 6] (llampc.mpc.constraints: strip, track_corridor; setupNLP.track_corridor on
     the device): every look-ahead cost gains corridor_weight x the summed squared slacks of the
     rollout's positions on the half-planes, so a candidate that leaves the track is ranked behind
-    one that stays (llampc_plan_corridor; 'rk4' and 'euler_nlp', the shared xref)."""
+    one that stays (llampc_plan_corridor; 'rk4' and 'euler_nlp', the shared xref).
+    track_corridor=True (after bank.set_track(track)): that corridor built inside the launch, along the
+    previous tick's chosen rollout shifted one step, half-width track_width / 2 - corridor_margin — no
+    geometry on the host and no path moved between ticks (llampc_plan_track; 'rk4').  The first tick,
+    and any tick after another kind of launch on the bank, runs without a corridor
+    (bank.set_corridor_path seeds one)."""
     U = np.asarray(U_cand, dtype=np.float64)
     if U.ndim == 2:
         U = U[None]
@@ -87,7 +93,8 @@ def plan(bank: ModelBank, x_t, u_prev, x_prev, xref, U_cand, uprev=None, Ts=0.02
         uprev, Ts=Ts, K=K, integrator=integrator, do_lookback=do_lookback, do_lookahead=True,
         current_model=current_model, nan_policy=nan_policy, cost=cost, return_errors=return_errors,
         return_window_mean=return_window_mean, return_costs=return_costs,
-        raceline_start=raceline_start, corridor=corridor, corridor_weight=corridor_weight)
+        raceline_start=raceline_start, corridor=corridor, corridor_weight=corridor_weight,
+        track_corridor=track_corridor, corridor_margin=corridor_margin)
     return result_from_out(o, U, lookback_err=err,
                            window_mean=wm if (wm is not None and o.window_full) else None,
                            costs=costs)
