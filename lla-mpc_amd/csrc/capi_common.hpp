@@ -1,7 +1,9 @@
-// capi_common.hpp — what the C ABI's translation units share (capi.hip: errors, bank, plan and
-// batch calls; capi_xchg.hip: RCCL, mailboxes, exchange; capi_ctl.hip: the controller;
-// capi_nlp.hip: the NLP solver; capi_nlp_batch.hip: the batched NLP solver): error reporting, the owners of device and pinned memory, the
-// handle structs and the few functions one file calls in another.  Nothing here is exported.
+// capi_common.hpp — what the C ABI's translation units share (capi.hip: errors, the bank's lifecycle,
+// the raceline upload; capi_plan.hip: the plan tick and its entries, the track entries; capi_batch.hip:
+// the raw batch calls and the merge; capi_xchg.hip: RCCL, mailboxes, exchange; capi_ctl.hip: the
+// controller; capi_nlp.hip: the NLP solver; capi_nlp_batch.hip: the batched NLP solver): error
+// reporting, the owners of device and pinned memory, the handle structs and the few functions one file
+// calls in another.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -148,7 +150,7 @@ struct llampc_comm {
 // has the comm's device current).
 int comm_all_gather(llampc_comm* c, const void* send, void* recv, size_t count, bool words, hipStream_t s);
 
-// ---- the bank (capi.hip) ------------------------------------------------------------
+// ---- the bank (capi.hip; its ticks: capi_plan.hip) ------------------------------------------------------------
 struct llampc_bank {
   int device = 0;
   int cus = 0;                           // the device's CU count, read at create (0: unknown)
@@ -210,14 +212,17 @@ struct llampc_bank {
   llampc::TrackPathState trk_path{0};    // the host's half of the path rule
   int32_t trk_last_H = 0;                // the horizon of the last launch if it was a track tick, else 0
 };
-// A track tick's own arguments beside the plan input.
-struct TrackTick {
-  double weight, margin;
-};
 static inline llampc::BankView bank_view(const llampc_bank& b) {
   return {b.d_params.get(), b.n, b.goff, b.veh, b.d_ring.get(), b.W, b.slot, b.d_wmean.get(),
           b.d_am_val.get(), b.d_am_idx.get(), b.d_tk_val.get(), b.d_tk_idx.get(),
           b.d_rl.get(), b.rl_n, b.rl_M, b.rl_hmin, b.rl_vmax};
+}
+// ... and what a plan tick takes beside it (px: the fused exchange's mailbox, or null).
+static inline llampc::PlanView plan_view(const llampc_bank& b, const llampc_mailbox* px) {
+  return {bank_view(b), b.d_best_cand.get(), b.d_best_cost.get(), b.d_pv.get(), b.d_pidx.get(), b.d_pnf.get(),
+          b.d_la_tag.get(), b.d_blk_tag.get(), b.d_wq.get(), b.d_tickets.get(), b.d_xref_pm.get(),
+          b.d_track.get(), b.tr_n, b.tr_L, b.tr_width, b.d_trk.get(), b.d_trk_flags.get(), b.d_hp_tag.get(),
+          px ? px->d_box.get() : nullptr, px ? px->world : 0, px ? px->rank : 0, px ? px->bound : 0};
 }
 
 // Cancels the armed controller launch waiting on the bank's stream, if any (capi_ctl.hip): the
@@ -225,16 +230,12 @@ static inline llampc::BankView bank_view(const llampc_bank& b) {
 void bank_disarm(llampc_bank* b);
 // The bank's own stream on a hardware queue of its own (the caller holds b->mu; nothing armed).
 int bank_dedicate(llampc_bank* b);
+// plan_in_refused of the bank's facts, reported through fail() (capi_plan.hip; the caller holds b->mu
+// or reads a bank nothing else configures).
 int check_plan_in(const llampc_bank* b, const llampc_plan_in* in);
-// The tick on device pointers: ONE launch (look-back + look-ahead + completion).  host_tag:
-// host completion; pk: the inputs as kernel arguments; px: the fused peer exchange; cor: the
-// look-ahead's corridor (device half-planes and weight; never with pk or px); tt: the track tick (the
-// corridor built in the launch from the bank's track and path state; never with pk, px or cor).
-int plan_launch(llampc_bank* b, const llampc_plan_in& in, llampc_plan_out* d_out, double* d_err, double* d_wmean,
-                double* d_cost, hipStream_t s, uint64_t* host_tag = nullptr, uint64_t host_seq = 0,
-                const llampc::InlinePack* pk = nullptr, llampc_mailbox* px = nullptr,
-                llampc_plan_out* px_merged = nullptr, const llampc::PlanCorridor* cor = nullptr,
-                const TrackTick* tt = nullptr);
+// The tick on device pointers (capi_plan.hip): ONE launch (look-back + look-ahead + completion) of what
+// `tick` names (capi_host.hpp PlanTick).  The bank's host state advances only once the launch was enqueued.
+int plan_launch(llampc_bank* b, const llampc_plan_in& in, const llampc::PlanTick& tick);
 inline hipStream_t pick_stream(llampc_bank* b, void* s) { return s ? (hipStream_t)s : b->stream; }
 
 // llampc_nlp_create's checks of a cfg (capi_nlp.hip), llampc_nlp_batch_create's too.

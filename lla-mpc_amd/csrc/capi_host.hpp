@@ -1,6 +1,7 @@
 // capi_host.hpp — the C ABI's host arithmetic (capi*.hip): sequence numbers, poll bounds, the
-// input pack, the window unroll, the launch-argument fields that come from the bank and the
-// controller launch's shape (the plan launch's: launch_shape.hpp).  Pure: no HIP runtime call, so
+// input pack, the window unroll, the launch-argument fields that come from the bank, the plan tick's
+// prepare / commit, its track state's layout and its entries' refusals, and the controller launch's
+// shape (the plan launch's: launch_shape.hpp).  Pure: no HIP runtime call, so
 // tests/native/capi_host.cpp runs all of it on a machine with no GPU.
 #pragma once
 #include <algorithm>
@@ -16,7 +17,37 @@
 #include "launch_shape.hpp"
 #include "nlp.hpp"
 
+struct llampc_mailbox;                   // capi_common.hpp
+
 namespace llampc {
+
+// The two types plan_launch (capi_common.hpp) is called with across translation units, so outside the
+// unnamed namespace.  A track tick's own arguments beside the plan input:
+struct TrackTick {
+  double weight, margin;
+};
+
+// What a tick takes beside the bank and the plan input; every field null or 0 unless named.
+// out: the record (device, or the device alias of the pinned host record); err [n], wmean [n], cost
+// [n][C]: device, or null.  host_tag / host_seq: host completion.  pk: the inputs as kernel arguments.
+// px: the fused peer exchange, merging into px_merged.  cor: the look-ahead's corridor (device
+// half-planes and weight; never with pk or px).  tt: the track tick (the corridor built in the launch
+// from the bank's track and path state; never with pk, px or cor).
+struct PlanTick {
+  llampc_plan_out* out = nullptr;
+  double* err = nullptr;
+  double* wmean = nullptr;
+  double* cost = nullptr;
+  hipStream_t stream = nullptr;
+  uint64_t* host_tag = nullptr;
+  uint64_t host_seq = 0;
+  const InlinePack* pk = nullptr;
+  llampc_mailbox* px = nullptr;
+  llampc_plan_out* px_merged = nullptr;
+  const PlanCorridor* cor = nullptr;
+  const TrackTick* tt = nullptr;
+};
+
 namespace {
 
 inline VehK make_veh(const llampc_vehicle& v) {
@@ -443,6 +474,302 @@ inline void bank_final(const BankView& b, FinalLaunch& f) {
   f.tk_val = b.tk_val;
   f.tk_idx = b.tk_idx;
 }
+
+// ---- the plan tick (capi_plan.hip plan_launch) ---------------------------------------------------
+// The track tick's device state (kernels.hpp PlanTrack), in the order it is allocated:
+//   d_trk        path copy 0 | path copy 1 (each [2][kPlanPathStride]) | cost 0, cost 1 | the read-back:
+//                path [2][kPlanPathStride] | hp [HMAX][6] | theta [HMAX] (kPlanTrackDbgDoubles in all)
+//   d_trk_flags  valid 0, valid 1 | the read-back's valid | the late word
+//   d_hp_tag     [12 HMAX] tagged half-plane words
+// The one statement of it: the allocation, the launch arguments, the seed and the read-back take it here.
+struct PlanTrackLayout {
+  size_t row = kPlanPathStride;          // a path's x row, then its y row
+  size_t path_doubles = 2 * row;         // one path copy
+  size_t rb_path = 2 * path_doubles + 2, rb_hp = rb_path + path_doubles, rb_theta = rb_hp + 6 * LLAMPC_HMAX;
+  size_t trk_doubles = rb_path + kPlanTrackDbgDoubles;
+  int flag_rb_valid = 2, flag_late = 3, flags = 4;
+  size_t hp_tag_words = 12 * (size_t)LLAMPC_HMAX;
+  constexpr size_t path(int r) const { return path_doubles * (size_t)r; }
+  constexpr size_t cost(int r) const { return 2 * path_doubles + (size_t)r; }
+  constexpr int valid(int r) const { return r; }
+};
+constexpr PlanTrackLayout plan_track_layout() { return {}; }
+
+// What a plan tick takes from a bank beside the BankView: the completion buffers, the track tables and
+// the track tick's state by address, and, of a fused exchange, the mailbox's table and sizes
+// (capi_common.hpp plan_view builds one per tick, on the stack).
+struct PlanView {
+  BankView bank;
+  int32_t* best_cand;  double* best_cost;            // [n]
+  double* pv;  int64_t* pidx;  int32_t* pnf;         // [blocks]
+  uint64_t* la_tag;  uint64_t* blk_tag;  uint64_t* wq;
+  unsigned* tickets;
+  double* xref_pm;                       // [n][H][2], reserved by the raceline tick
+  const double* track;                   // cx | cy | tt, [3][tr_n]
+  int32_t tr_n;
+  double tr_L, tr_width;
+  double* trk;  int32_t* trk_flags;  uint64_t* hp_tag;   // plan_track_layout
+  uint64_t* const* px_box;               // the mailbox (null: none)
+  int32_t px_G, px_rank;
+  uint64_t px_bound;
+};
+
+// The host state a tick reads and, once its launch was enqueued, advances.
+struct PlanTickState {
+  int32_t count, slot, W;                // the window: rows filled, the row written next
+  uint32_t seq, tseq;                    // the launch tag's sequence, the half-plane words'
+  int32_t trk_cur;                       // the path copy that holds the newest path
+  TrackPathState trk_path;
+  int32_t trk_last_H;
+  uint32_t px_seq;                       // the mailbox's sequence (ticks with px)
+};
+// A bank's (and, px not null, its mailbox's) state, and a prepared tick's next state applied to them.
+// Templates only so that the host harness runs them on plain structs of the same field names.
+template <class Bank, class Mailbox>
+inline PlanTickState plan_tick_state(const Bank& b, const Mailbox* px) {
+  return {b.count, b.slot, b.W, b.seq, b.tseq, b.trk_cur, b.trk_path, b.trk_last_H, px ? px->seq : 0};
+}
+template <class Bank, class Mailbox>
+inline void plan_tick_commit(Bank& b, Mailbox* px, const PlanTickState& next) {
+  b.count = next.count;
+  b.slot = next.slot;
+  b.seq = next.seq;
+  b.tseq = next.tseq;
+  b.trk_cur = next.trk_cur;
+  b.trk_path = next.trk_path;
+  b.trk_last_H = next.trk_last_H;
+  if (px) px->seq = next.px_seq;
+}
+
+// A tick's launch arguments (lbl / lal / trk: only where lb / la / tt say so) and the state after it.
+struct PlanPrep {
+  bool lb, la, tt;
+  LookbackLaunch lbl;
+  LookaheadLaunch lal;
+  FinalLaunch f;
+  PlanTrack trk;
+  PlanTickState next;
+};
+
+// One tick's arguments from the view, the state and what the caller asks for.  launch_plan sets the
+// shape's own fields (f.nb_* / f.do_*, the look-back's R, the raceline's wcap).
+inline PlanPrep plan_tick_prepare(const PlanView& v, const PlanTickState& st, const llampc_plan_in& in, const PlanTick& t) {
+  const BankView& bv = v.bank;
+  PlanPrep p{};
+  p.lb = in.do_lookback != 0;
+  p.la = in.do_lookahead != 0;
+  p.tt = t.tt != nullptr;
+  PlanTickState& nx = p.next = st;
+  if (p.lb) {
+    nx.count = std::min(st.count + 1, st.W);         // rt.py:354
+    nx.slot = (st.slot + 1) % st.W;
+  }
+  const int32_t full = nx.count >= st.W;             // rt.py:357
+  // polled completion whenever look-back blocks exist to host the poller (LLAMPC_NO_POLL=1:
+  // the ticket + last-block path, for A/B runs)
+  const int32_t poll = (p.lb && p.la && getenv("LLAMPC_NO_POLL") == nullptr) ? 1 : 0;
+  if (poll) nx.seq = next_seq(st.seq);
+  if (p.lb) {
+    LookbackLaunch& l = p.lbl;
+    bank_lookback(bv, l);
+    l.slot = st.slot;
+    l.x_prev = in.x_prev;
+    l.u_prev = in.u_prev;
+    l.x_now = in.x_now;
+    l.Ts = in.Ts;
+    l.full = full;
+    l.K = in.K;
+    l.nan_first = in.nan_policy == LLAMPC_NAN_FIRST;
+    l.err_out = t.err;
+    if (t.wmean) l.wm_buf = t.wmean;
+    l.wm_keep = t.wmean != nullptr;                  // else only the R > 1 second pass reads it
+  }
+  if (p.la) {
+    LookaheadLaunch& l = p.lal;
+    bank_lookahead(bv, in.integrator, l);
+    l.x0 = in.x_now;
+    l.U = in.U;
+    l.xref = in.xref;
+    l.uprev = in.uprev;
+    l.C = in.C;
+    l.H = in.H;
+    l.Ts = in.Ts;
+    l.cost = make_cost(in.cost, in.Ts);
+    l.cost_out = t.cost;
+    l.best_cand = v.best_cand;
+    l.best_cost = v.best_cost;
+    l.pv = v.pv;
+    l.pidx = v.pidx;
+    l.pnf = v.pnf;
+    l.xref_mode = in.xref_mode;
+    if (in.xref_mode == LLAMPC_XREF_RACELINE) {
+      l.rl = raceline_view(bv);          // wcap: set by launch_plan from the LDS it leaves
+      l.xref_pm = v.xref_pm;
+    }
+    l.la_tag = v.la_tag;
+    l.blk_tag = v.blk_tag;
+    l.seq = nx.seq;
+    l.poll = poll;
+    l.wq = v.wq;
+  }
+  FinalLaunch& f = p.f;
+  bank_final(bv, f);
+  f.out = t.out;
+  f.tickets = v.tickets;
+  f.full = full;
+  f.window_count = nx.count;
+  f.K = p.lb ? in.K : 0;
+  f.nan_first = in.nan_policy == LLAMPC_NAN_FIRST;
+  f.C = p.la ? in.C : 1;
+  f.current_model = in.current_model;
+  f.best_cand = v.best_cand;
+  f.best_cost = v.best_cost;
+  f.pv = v.pv;
+  f.pidx = v.pidx;
+  f.pnf = v.pnf;
+  f.la_tag = v.la_tag;
+  f.blk_tag = v.blk_tag;
+  f.seq = nx.seq;
+  f.poll = poll ? (int32_t)poll_units(poll_bound_ticks(bv.n, in.C, in.H), INT32_MAX) : 0;
+  f.host_tag = t.host_tag;
+  f.host_seq = t.host_seq;
+  if (t.px) {                            // fused peer exchange (llampc_plan_exchange)
+    nx.px_seq = next_seq(st.px_seq);
+    f.px_box = v.px_box;
+    f.px_merged = t.px_merged;
+    f.px_G = v.px_G;
+    f.px_rank = v.px_rank;
+    f.px_seq = nx.px_seq;
+    f.px_bound = (uint32_t)poll_units(v.px_bound, UINT32_MAX);
+  }
+  f.wq = v.wq;
+  // the track tick: the read copy is the one the launch before wrote (or llampc_bank_set_path), the
+  // write copy the other; the half-plane words' own sequence
+  if (t.tt) {
+    constexpr PlanTrackLayout L = plan_track_layout();
+    const size_t tn = (size_t)v.tr_n;
+    const int rd = st.trk_cur, wr = rd ^ 1;
+    PlanTrack& k = p.trk;
+    nx.tseq = next_seq(st.tseq);
+    nx.trk_cur = wr;
+    k.trk = TrackK{v.track, v.track + tn, v.track + 2 * tn, v.tr_n, 0, v.tr_L};
+    k.hw = v.tr_width / 2 - t.tt->margin;
+    k.weight = t.tt->weight;
+    k.hp_tag = v.hp_tag;
+    k.path_rd = v.trk + L.path(rd);
+    k.path_wr = v.trk + L.path(wr);
+    k.valid_rd = v.trk_flags + L.valid(rd);
+    k.valid_wr = v.trk_flags + L.valid(wr);
+    k.cost_wr = v.trk + L.cost(wr);
+    k.dbg = v.trk + L.rb_path;
+    k.dbg_valid = v.trk_flags + L.flag_rb_valid;
+    k.late = reinterpret_cast<uint32_t*>(v.trk_flags + L.flag_late);
+    k.seq = nx.tseq;
+    k.poll = (uint32_t)poll_units(poll_bound_ticks(bv.n, in.C, in.H), INT32_MAX);
+    k.path_ok = track_path_offered(st.trk_path, in.H) ? 1 : 0;
+  }
+  nx.trk_path = track_path_next(st.trk_path, t.tt ? kPathTrackTick : kPathOtherLaunch, in.H);
+  nx.trk_last_H = t.tt ? in.H : 0;
+  return p;
+}
+
+// plan_shape of a look-ahead alone, for what no bank decides: of n models (they matter to the LPM
+// only; a plan input's own questions take n = 1), with the inline pack or a corridor offered.
+inline PlanShape lookahead_shape(int64_t n, bool la, int32_t C, int32_t H, int32_t integrator, int32_t xref_mode,
+                                 int32_t share, bool pack, bool corridor, int32_t track_n = 0) {
+  PlanShapeIn s{};
+  s.n = n;
+  s.la = la;
+  s.C = C;
+  s.H = H;
+  s.integrator = integrator;
+  s.xref_mode = xref_mode;
+  s.share = share;
+  s.pack = pack;
+  s.corridor = corridor;
+  s.track_n = track_n;
+  return plan_shape(s, 0);
+}
+
+// ---- what the tick entries refuse before anything is enqueued ------------------------------------
+// Each returns LLAMPC_OK, or the code with the message in buf.  The bank facts they are decided by:
+struct PlanBankFacts {
+  int64_t n;
+  bool raceline;                         // llampc_bank_set_raceline was called
+  int32_t tr_n;                          // 0: no track set
+  double tr_width;
+  bool async_pending;
+};
+#define LLAMPC_REFUSE(code, ...) return (std::snprintf(buf, nbuf, __VA_ARGS__), (code))
+
+inline int plan_in_refused(const PlanBankFacts& b, const llampc_plan_in* in, char* buf, size_t nbuf) {
+  if (!in) LLAMPC_REFUSE(LLAMPC_E_ARG, "plan input is NULL");
+  if (in->do_lookback && (in->K < 1 || in->K > LLAMPC_KMAX))
+    LLAMPC_REFUSE(LLAMPC_E_ARG, "K=%d outside [1, %d]", in->K, LLAMPC_KMAX);
+  if (in->do_lookback && (!in->x_prev || !in->u_prev || !in->x_now))
+    LLAMPC_REFUSE(LLAMPC_E_ARG, "look-back needs x_prev, u_prev and x_now");
+  if (in->do_lookahead) {
+    if (in->C < 1 || in->H < 1) LLAMPC_REFUSE(LLAMPC_E_ARG, "C=%d H=%d must be >= 1", in->C, in->H);
+    if ((int64_t)in->C * in->H > (1 << 26)) LLAMPC_REFUSE(LLAMPC_E_ARG, "C*H too large");
+    if (!in->x_now || !in->U || !in->xref || !in->uprev)
+      LLAMPC_REFUSE(LLAMPC_E_ARG, "look-ahead needs x_now, U, xref and uprev");
+    if (in->integrator < LLAMPC_RK4 || in->integrator > LLAMPC_RK6)
+      LLAMPC_REFUSE(LLAMPC_E_ARG, "unknown integrator %d", in->integrator);
+    if (in->xref_mode != LLAMPC_XREF_GIVEN && in->xref_mode != LLAMPC_XREF_RACELINE)
+      LLAMPC_REFUSE(LLAMPC_E_ARG, "unknown xref_mode %d", in->xref_mode);
+    if (in->xref_mode == LLAMPC_XREF_RACELINE && !b.raceline)
+      LLAMPC_REFUSE(LLAMPC_E_STATE, "xref_mode RACELINE needs llampc_bank_set_raceline first");
+    if ((b.n + 1) * (int64_t)in->C <= 0 || b.n > INT64_MAX / std::max(1, in->C) - 1)
+      LLAMPC_REFUSE(LLAMPC_E_ARG, "n*C overflows");
+  }
+  if (!in->do_lookback && !in->do_lookahead) LLAMPC_REFUSE(LLAMPC_E_ARG, "nothing to do: look-back and look-ahead both off");
+  if (!(in->Ts > 0) || !std::isfinite(in->Ts)) LLAMPC_REFUSE(LLAMPC_E_ARG, "Ts must be finite > 0");
+  return LLAMPC_OK;
+}
+
+// A corridor tick (llampc_plan_corridor, llampc_lookahead_corridor): no look-ahead, RK6, the per-model
+// raceline reference — plan_shape's refusals of the corridor's modes, in its words (the rest of the
+// input is plan_in_refused's to judge).
+inline int corridor_mode_refused(const llampc_plan_in* in, char* buf, size_t nbuf) {
+  const char* why =
+      lookahead_shape(1, in->do_lookahead != 0, in->C, in->H, in->integrator, in->xref_mode, 1, false, true).refuse;
+  if (why == kNoCorridorLookahead || why == kNoCorridorRk6 || why == kNoCorridorRaceline) LLAMPC_REFUSE(LLAMPC_E_ARG, "%s", why);
+  return LLAMPC_OK;
+}
+
+// A track tick (llampc_plan_track, llampc_plan_track_async): no track, an async tick outstanding
+// (LLAMPC_E_STATE), then plan_shape's refusals of the track tick's modes, in its words, and a weight or
+// margin track_tick_invalid names.
+inline int track_tick_refused(const PlanBankFacts& b, const llampc_plan_in* in, const TrackTick& tt, char* buf, size_t nbuf) {
+  if (!b.tr_n) LLAMPC_REFUSE(LLAMPC_E_STATE, "no track set: call llampc_bank_set_track first");
+  if (b.async_pending) LLAMPC_REFUSE(LLAMPC_E_STATE, "an async tick is outstanding: call llampc_plan_wait");
+  if (in) {
+    const char* why = lookahead_shape(1, in->do_lookahead != 0, in->C, in->H, in->integrator, in->xref_mode, 1, false,
+                                      false, b.tr_n).refuse;
+    if (why == kNoTrackLookahead || why == kNoTrackRk6 || why == kNoTrackEuler || why == kNoTrackRaceline)
+      LLAMPC_REFUSE(LLAMPC_E_ARG, "%s", why);
+  }
+  if (const char* why = track_tick_invalid(tt.weight, tt.margin, b.tr_width)) LLAMPC_REFUSE(LLAMPC_E_ARG, "track tick: %s", why);
+  return LLAMPC_OK;
+}
+
+// A host-pointer tick entry's refusals up to the point where it disarms the bank, in the entry's one
+// order: hp (llampc_plan_corridor) the corridor's modes first — LLAMPC_E_ARG whatever else the bank
+// lacks; tt (the track entries) the track tick's, in their table's order; the plan input; the track
+// tick's horizon; the corridor's rows and weight (H is valid by then).  An outstanding async tick is
+// refused by the track tick's table here, by every other entry after the disarm.
+inline int plan_entry_refused(const PlanBankFacts& b, const llampc_plan_in* in, const double* hp, double weight,
+                              const TrackTick* tt, char* buf, size_t nbuf) {
+  int rc;
+  if (hp && in && (rc = corridor_mode_refused(in, buf, nbuf))) return rc;
+  if (tt && (rc = track_tick_refused(b, in, *tt, buf, nbuf))) return rc;
+  if ((rc = plan_in_refused(b, in, buf, nbuf))) return rc;
+  if (tt && in->H > LLAMPC_HMAX) LLAMPC_REFUSE(LLAMPC_E_ARG, "H=%d above %d (the path state's horizon)", in->H, LLAMPC_HMAX);
+  if (hp)
+    if (const char* why = corridor_invalid(hp, in->H, weight)) LLAMPC_REFUSE(LLAMPC_E_ARG, "corridor: %s", why);
+  return LLAMPC_OK;
+}
+#undef LLAMPC_REFUSE
 
 // The launch shape of a controller tick (ctl.hip ctl_kernel<lpm, *>): the look-ahead's lanes per
 // rollout, lane group, candidates per lane and models per block, whether its input terms are

@@ -220,10 +220,15 @@ int llampc_plan_exchange(llampc_bank* b, const llampc_plan_in* in, void* d_local
   if ((rc = mailbox_sync(mb))) return rc;   // the peers are open: publish the table once
   const bool split = getenv("LLAMPC_PEER_SPLIT") != nullptr;   // A/B: separate kernel
   const bool fusable = !in->do_lookahead || (in->integrator == LLAMPC_RK4 && in->xref_mode == LLAMPC_XREF_GIVEN);
-  if (!split && fusable && mb->world <= kPeerFuseMax)
-    return plan_launch(b, *in, (llampc_plan_out*)d_local, nullptr, nullptr, nullptr, s, nullptr, 0, nullptr,
-                       mb, (llampc_plan_out*)d_merged);
-  rc = plan_launch(b, *in, (llampc_plan_out*)d_local, nullptr, nullptr, nullptr, s);
+  PlanTick t;
+  t.out = (llampc_plan_out*)d_local;
+  t.stream = s;
+  if (!split && fusable && mb->world <= kPeerFuseMax) {
+    t.px = mb;
+    t.px_merged = (llampc_plan_out*)d_merged;
+    return plan_launch(b, *in, t);
+  }
+  rc = plan_launch(b, *in, t);
   if (rc) return rc;
   lm.unlock();                           // llampc_exchange_peer takes it
   return llampc_exchange_peer(mb, d_local, d_merged, in->nan_policy, s);

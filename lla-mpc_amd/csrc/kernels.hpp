@@ -1,4 +1,4 @@
-// kernels.hpp — internal launch interface between the C ABI (capi.hip) and the HIP
+// kernels.hpp — internal launch interface between the C ABI (capi*.hip) and the HIP
 // kernels (kernels.hip).  Every pointer here is a device pointer; launches are async.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // launch_shape.hpp — the shape of a plan launch (plan_shape): the kernel family and variant a tick
 // takes, its block counts, its LDS request and what it refuses, with the sizing functions and LDS
 // layout constants the rule is made of.  The one statement of that rule: launch_plan (kernels.hip)
-// and the C ABI's variant entries, inline-pack decision and corridor mode refusals (capi.hip) take
+// and the C ABI's variant entries, inline-pack decision and mode refusals (capi_plan.hip) take
 // it from here.  No HIP runtime call: tests/native/capi_host.cpp runs it on a machine with no GPU.
 // Included by dev_wave.hpp (the constants the device code lays its LDS out by) and capi_host.hpp.
 #pragma once
@@ -157,13 +157,13 @@ struct PlanShapeIn {
 enum PlanFamily { kPlanPlain = 0, kPlanInline = 1, kPlanCorridor = 2, kPlanTrack = 3 };
 
 // Why plan_shape refuses a launch (PlanShape::refuse points at one of these).  The corridor's
-// three mode refusals are the C ABI's messages (capi.hip check_corridor_mode).
+// three mode refusals are the C ABI's messages (capi_host.hpp corridor_mode_refused).
 inline constexpr char kNoCorridorLookahead[] = "the corridor belongs to the look-ahead: do_lookahead is 0";
 inline constexpr char kNoCorridorRk6[] = "the corridor look-ahead has no RK6 rollout";
 inline constexpr char kNoCorridorRaceline[] =
     "the corridor look-ahead takes the given xref only (not LLAMPC_XREF_RACELINE)";
 inline constexpr char kNoCorridorInputs[] = "the corridor launch takes device inputs and no fused peer exchange";
-// The track tick's refusals (capi.hip check_track_tick passes the mode ones on).
+// The track tick's refusals (capi_host.hpp track_tick_refused passes the mode ones on).
 inline constexpr char kNoTrackLookahead[] = "the track tick's corridor belongs to the look-ahead: do_lookahead is 0";
 inline constexpr char kNoTrackRk6[] = "the track tick has no RK6 rollout";
 inline constexpr char kNoTrackEuler[] = "the track tick has no NLP-Euler rollout (llampc_plan_corridor takes host-built rows)";

@@ -1,6 +1,7 @@
 """csrc/capi_host.hpp (the C ABI's pure host helpers: tick numbers, poll bounds, the input
-pack, the window unroll, the raceline view, the launch fields that come from the bank and the
-controller launch's shape) and csrc/launch_shape.hpp (the plan launch's shape) compiled for the
+pack, the window unroll, the raceline view, the launch fields that come from the bank, the plan
+tick's prepare / commit, its track state's layout, its entries' refusals and the controller launch's
+shape) and csrc/launch_shape.hpp (the plan launch's shape) compiled for the
 host with AddressSanitizer and UBSan and run on the CPU.  The harness (tests/native/capi_host.cpp)
 prints values; what they must be is worked out here."""
 import os
@@ -560,3 +561,295 @@ def test_ctl_shape(harness, nat, monkeypatch):
     assert (w["nslots"], w["nb_la"], w["nb_lb"]) == (1, 1, 1)
     a, b = ctl(100, 96, 20, 10, 700, 0, 1, 0, 0), ctl(100, 96, 20, 10, 700, 0, 1, 1, 0)
     assert a["s4"] == 1 and b["s4"] == 0 and b["lds"] < a["lds"] and {**a, "s4": 0, "lds": 0, "poll_off": 0} == {**b, "lds": 0, "poll_off": 0}
+
+
+# ---- the plan tick's host path (capi_host.hpp plan_tick_prepare / plan_tick_commit, plan_track_layout, ----
+# ---- the entries' refusals) --------------------------------------------------------------------------
+# The harness's `prep` mode runs ticks of one kind on a fake bank (tests/native/capi_host.cpp fake_plan_view:
+# distinct addresses that are never dereferenced) and prints every field of the launch structs, of the next
+# state and of the bank after plan_tick_commit; prep_model restates kernels.hpp's comments on them.
+HMAX, PATH_STRIDE = 64, 65
+VIEW = dict(params=0x1000, n=5, goff=70, lf=0.5, mass=0.25, ring=0x2000, W=3, wmean=0x3000, am_val=0x4000, am_idx=0x5000,
+            tk_val=0x6000, tk_idx=0x7000, rl=0x80000, rl_n=5, rl_M=2, rl_hmin=0.25, rl_vmax=3.5, best_cand=0x9000,
+            best_cost=0xA000, pv=0xB000, pidx=0xC000, pnf=0xD000, la_tag=0xE000, blk_tag=0xF000, wq=0x10000, tickets=0x11000,
+            xref_pm=0x12000, track=0x20000, tr_n=4, tr_L=8.0, tr_width=2.4, trk=0x30000, trk_flags=0x40000, hp_tag=0x50000,
+            px_box=0x60000, px_G=2, px_rank=1, px_bound=10 ** 9)
+IN = dict(x_prev=0x100000, u_prev=0x100100, x_now=0x100200, U=0x100300, xref=0x100400, uprev=0x100500)
+TICK = dict(out=0x200000, err=0x201000, wmean=0x202000, cost=0x203000, host_tag=0x204000, host_seq=9, px_merged=0x205000)
+PREP_DEFAULTS = dict(lb=1, la=1, xref_mode=XREF_GIVEN, integrator=RK4, C=2, H=3, K=4, Ts=0.02, nan_policy=0, current_model=3,
+                     err=0, wmean=0, cost=0, host=0, pk=0, cor=0, px=0, tt=0, tw=1e4, margin=0.05,
+                     count=1, slot=2, W=3, seq=7, tseq=11, trk_cur=0, path_H=0, last_H=0, px_seq=5, ticks=1)
+
+
+def next_seq(s):
+    return 2 if s == 0xFFFFFFFF else s + 1
+
+
+def prep_model(env, **kw):
+    """[one dict per tick] of every printed field, as strings the way the harness prints them."""
+    a = dict(PREP_DEFAULTS, **kw)
+    V, hx, g = VIEW, (lambda p: format(p, "x")), (lambda d: repr(float(d)))
+    st = dict(count=a["count"], slot=a["slot"], W=a["W"], seq=a["seq"], tseq=a["tseq"], trk_cur=a["trk_cur"],
+              trk_path=a["path_H"], trk_last_H=a["last_H"], px_seq=a["px_seq"] if a["px"] else 0)
+    box = a["px_seq"]
+    lb, la, tt, px = bool(a["lb"]), bool(a["la"]), bool(a["tt"]), bool(a["px"])
+    C, H, K, Ts = a["C"], a["H"], a["K"], a["Ts"]
+    nan_first = int(a["nan_policy"] == 0)
+    bound = poll_model(V["n"], C, H, max(0.0, float(env.get("LLAMPC_POLL_BOUND_S", 2.0))),
+                       max(0.0, float(env.get("LLAMPC_POLL_STEP_NS", 40.0))))[1]
+    ticks = []
+    for _ in range(a["ticks"]):
+        nx = dict(st)
+        if lb:                                   # the window advances with a look-back only, and saturates at W
+            nx["count"], nx["slot"] = min(st["count"] + 1, st["W"]), (st["slot"] + 1) % st["W"]
+        full = int(nx["count"] >= st["W"])
+        poll = int(lb and la and "LLAMPC_NO_POLL" not in env)     # a look-back block hosts the poller
+        if poll:
+            nx["seq"] = next_seq(st["seq"])
+        o = {"has.lb": int(lb), "has.la": int(la), "has.tt": int(tt)}
+        if lb:
+            o.update({"lb.params": hx(V["params"]), "lb.n": V["n"], "lb.goff": V["goff"], "lb.veh.lf": g(V["lf"]),
+                      "lb.veh.mass": g(V["mass"]), "lb.x_prev": hx(IN["x_prev"]), "lb.u_prev": hx(IN["u_prev"]),
+                      "lb.x_now": hx(IN["x_now"]), "lb.Ts": g(Ts), "lb.ring": hx(V["ring"]), "lb.W": V["W"],
+                      "lb.slot": st["slot"], "lb.full": full, "lb.K": K, "lb.nan_first": nan_first, "lb.R": 0,
+                      "lb.wm_keep": int(bool(a["wmean"])), "lb.err_out": hx(TICK["err"] if a["err"] else 0),
+                      "lb.wm_buf": hx(TICK["wmean"] if a["wmean"] else V["wmean"]), "lb.am_val": hx(V["am_val"]),
+                      "lb.am_idx": hx(V["am_idx"]), "lb.tk_val": hx(V["tk_val"]), "lb.tk_idx": hx(V["tk_idx"])})
+        if la:
+            nlp = a["integrator"] == EULER_NLP
+            race = a["xref_mode"] == XREF_RACELINE
+            m = V["rl_n"] - 1
+            xy = V["rl"] + 8 * V["rl_n"]
+            o.update({"la.params": hx(V["params"]), "la.n": V["n"], "la.goff": V["goff"], "la.veh.lf": g(V["lf"]),
+                      "la.veh.mass": g(V["mass"]), "la.veh.input_acc": int(not nlp), "la.veh.approx": int(not nlp),
+                      "la.x0": hx(IN["x_now"]), "la.U": hx(IN["U"]), "la.xref": hx(IN["xref"]), "la.uprev": hx(IN["uprev"]),
+                      "la.C": C, "la.H": H, "la.integrator": a["integrator"], "la.Ts": g(Ts),
+                      "la.cost.umin0": g(-0.1), "la.cost.umin1": g(-0.35), "la.cost.umax0": g(1.0), "la.cost.umax1": g(0.35),
+                      "la.cost.dmax0": g(-1.0), "la.cost.dmax1": g(2.0 * Ts * (1.0 + 1e-9)), "la.cost.enforce": 1,
+                      "la.cost.pad": 0, "la.cost_out": hx(TICK["cost"] if a["cost"] else 0), "la.best_cand": hx(V["best_cand"]),
+                      "la.best_cost": hx(V["best_cost"]), "la.pv": hx(V["pv"]), "la.pidx": hx(V["pidx"]), "la.pnf": hx(V["pnf"]),
+                      "la.xref_mode": a["xref_mode"],
+                      "la.rl.knots": hx(V["rl"] if race else 0), "la.rl.xy": hx(xy if race else 0),
+                      "la.rl.speed": hx(xy + 8 * 8 * m if race else 0),
+                      "la.rl.mus": hx(xy + 8 * 8 * m + 8 * 4 * m * V["rl_M"] if race else 0),
+                      "la.rl.n": V["rl_n"] if race else 0, "la.rl.M": V["rl_M"] if race else 0, "la.rl.wcap": 0,
+                      "la.rl.hmin": g(V["rl_hmin"] if race else 0), "la.rl.vmax": g(V["rl_vmax"] if race else 0),
+                      "la.xref_pm": hx(V["xref_pm"] if race else 0), "la.la_tag": hx(V["la_tag"]), "la.blk_tag": hx(V["blk_tag"]),
+                      "la.seq": nx["seq"], "la.poll": poll, "la.wq": hx(V["wq"])})
+            for i in range(4):
+                o.update({f"la.cost.Q{i}": g(1 + i), f"la.cost.R{i}": g(10 + i), f"la.cost.P{i}": g(20 + i)})
+        if px:
+            nx["px_seq"] = next_seq(st["px_seq"])
+        o.update({"f.out": hx(TICK["out"]), "f.tickets": hx(V["tickets"]), "f.do_lb": 0, "f.do_la": 0, "f.full": full,
+                  "f.window_count": nx["count"], "f.K": K if lb else 0, "f.nan_first": nan_first, "f.nb_lb": 0, "f.nb_la": 0,
+                  "f.C": C if la else 1, "f.current_model": a["current_model"], "f.n": V["n"], "f.goff": V["goff"],
+                  "f.params": hx(V["params"]), "f.best_cand": hx(V["best_cand"]), "f.best_cost": hx(V["best_cost"]),
+                  "f.am_val": hx(V["am_val"]), "f.am_idx": hx(V["am_idx"]), "f.tk_val": hx(V["tk_val"]),
+                  "f.tk_idx": hx(V["tk_idx"]), "f.pv": hx(V["pv"]), "f.pidx": hx(V["pidx"]), "f.pnf": hx(V["pnf"]),
+                  "f.la_tag": hx(V["la_tag"]), "f.blk_tag": hx(V["blk_tag"]), "f.seq": nx["seq"], "f.poll": bound if poll else 0,
+                  "f.host_tag": hx(TICK["host_tag"] if a["host"] else 0), "f.host_seq": TICK["host_seq"] if a["host"] else 0,
+                  "f.px_box": hx(V["px_box"] if px else 0), "f.px_merged": hx(TICK["px_merged"] if px else 0),
+                  "f.px_G": V["px_G"] if px else 0, "f.px_rank": V["px_rank"] if px else 0, "f.px_seq": nx["px_seq"] if px else 0,
+                  "f.px_bound": min(max((V["px_bound"] + 0xFFFF) >> 16, 1), UINT32_MAX) if px else 0, "f.wq": hx(V["wq"])})
+        if tt:
+            rd, wr = st["trk_cur"], st["trk_cur"] ^ 1
+            nx["tseq"], nx["trk_cur"] = next_seq(st["tseq"]), wr
+            path = lambda r: V["trk"] + 8 * 2 * PATH_STRIDE * r
+            costs = V["trk"] + 8 * 4 * PATH_STRIDE
+            o.update({"trk.cx": hx(V["track"]), "trk.cy": hx(V["track"] + 8 * V["tr_n"]), "trk.tt": hx(V["track"] + 16 * V["tr_n"]),
+                      "trk.n": V["tr_n"], "trk.npad": 0, "trk.L": g(V["tr_L"]), "trk.hw": g(V["tr_width"] / 2 - a["margin"]),
+                      "trk.weight": g(a["tw"]), "trk.hp_tag": hx(V["hp_tag"]), "trk.path_rd": hx(path(rd)),
+                      "trk.path_wr": hx(path(wr)), "trk.valid_rd": hx(V["trk_flags"] + 4 * rd),
+                      "trk.valid_wr": hx(V["trk_flags"] + 4 * wr), "trk.cost_wr": hx(costs + 8 * wr), "trk.dbg": hx(costs + 16),
+                      "trk.dbg_valid": hx(V["trk_flags"] + 8), "trk.late": hx(V["trk_flags"] + 12), "trk.seq": nx["tseq"],
+                      "trk.poll": bound, "trk.path_ok": int(st["trk_path"] != 0 and st["trk_path"] == H), "trk.pad": 0})
+        nx["trk_path"] = H if tt else 0                              # track_path_next: a track tick leaves its H
+        nx["trk_last_H"] = H if tt else 0
+        o.update({f"next.{k}": v for k, v in nx.items()})
+        if px:
+            box = nx["px_seq"]
+        o.update({f"bank.{k}": v for k, v in nx.items() if k != "px_seq"})
+        o["box.seq"] = box
+        ticks.append({k: (v if isinstance(v, str) else str(v)) for k, v in o.items()})
+        st = nx
+    return ticks
+
+
+@pytest.fixture(scope="module")
+def prep(harness):
+    """prep(env=None, **fields): the harness's ticks, each checked against prep_model field by field."""
+    def run(env=None, **fields):
+        rows = [ln.split() for ln in harness("prep", *(f"{k}={v}" for k, v in fields.items()), env=env).strip().splitlines()]
+        want = prep_model(env or {}, **fields)
+        got = [dict() for _ in want]
+        for key, val in rows:
+            t, _, name = key.partition(".")
+            got[int(t[1:])][name] = val
+        for t, (g_, w_) in enumerate(zip(got, want)):
+            assert set(g_) == set(w_), (t, set(g_) ^ set(w_))
+            for k in w_:
+                dbl = k.split(".")[-1] in ("lf", "mass", "Ts", "hmin", "vmax", "L", "hw", "weight") or ".cost." in k and \
+                    k not in ("la.cost.enforce", "la.cost.pad")
+                assert (float(g_[k]) == float(w_[k])) if dbl else (g_[k] == w_[k]), (fields, t, k, g_[k], w_[k])
+        return got
+    return run
+
+
+PREP_KINDS = {
+    "lookback": dict(la=0, err=1, wmean=1),
+    "lookahead": dict(lb=0, cost=1),
+    "both_polled": dict(),
+    "both_host": dict(host=1, pk=1),
+    "raceline": dict(xref_mode=XREF_RACELINE),
+    "exchange": dict(px=1),
+    "corridor": dict(cor=1, cost=1),
+    "track": dict(tt=1, path_H=3),
+    "track_no_lookback": dict(tt=1, lb=0, path_H=4),
+    "nlp_euler": dict(integrator=EULER_NLP),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(PREP_KINDS))
+def test_plan_tick_prepare(prep, kind):
+    """Every field of the launch structs and of the next state, for each kind of tick, polled and under
+    LLAMPC_NO_POLL; what prepare never reads (pk, cor) changes nothing."""
+    kw = PREP_KINDS[kind]
+    for env in (None, {"LLAMPC_NO_POLL": "1"}, {"LLAMPC_POLL_BOUND_S": "0.5"}):
+        prep(env, **kw)
+    if kind == "corridor":
+        assert prep(None, **kw) == prep(None, cost=1) == prep(None, cost=1, pk=1)
+
+
+def test_plan_tick_state_rules(prep):
+    """seq advances on polled ticks only; tseq and trk_cur on track ticks only; slot and count with a
+    look-back only, count saturating at W; trk_path as track_path_next; the mailbox's seq with px only."""
+    nxt = lambda env=None, **kw: {k[5:]: int(v) for k, v in prep(env, **kw)[0].items() if k.startswith("next.")}
+    base = dict(count=1, slot=2, W=3, seq=7, tseq=11, trk_cur=0, trk_path=0, trk_last_H=0, px_seq=0)
+    assert nxt() == dict(base, count=2, slot=0, seq=8)
+    assert nxt({"LLAMPC_NO_POLL": "1"}) == dict(base, count=2, slot=0)
+    assert nxt(lb=0) == base and nxt(la=0) == dict(base, count=2, slot=0)
+    assert nxt(count=3, slot=1) == dict(base, count=3, slot=2, seq=8)
+    assert nxt(count=0, slot=0, W=1) == dict(base, count=1, slot=0, W=1, seq=8)
+    assert nxt(px=1) == dict(base, count=2, slot=0, seq=8, px_seq=6)
+    assert nxt(px=1, px_seq=0xFFFFFFFF)["px_seq"] == 2
+    assert nxt(tt=1, lb=0) == dict(base, tseq=12, trk_cur=1, trk_path=3, trk_last_H=3)
+    assert nxt(tt=1, trk_cur=1, tseq=0xFFFFFFFF) == dict(base, count=2, slot=0, seq=8, tseq=2, trk_cur=0, trk_path=3, trk_last_H=3)
+    assert nxt(path_H=3, last_H=3) == dict(base, count=2, slot=0, seq=8)          # any other launch clears the path
+    # the path is offered only at the tick's own horizon
+    ok = lambda **kw: int(prep(None, tt=1, **kw)[0]["trk.path_ok"])
+    assert [ok(path_H=3), ok(path_H=4), ok(path_H=0), ok(path_H=3, H=4)] == [1, 0, 0, 0]
+
+
+def test_plan_tick_chain(prep):
+    """Three ticks chained through plan_tick_commit across seq = 0xFFFFFFFF (never 0, the parity alternates);
+    the track tick reads one path copy and writes the other, and the two swap on the next tick."""
+    ticks = prep(None, tt=1, px=0, ticks=3, seq=0xFFFFFFFE, tseq=0xFFFFFFFE, count=0, slot=0, W=2)
+    assert [int(t["f.seq"]) for t in ticks] == [0xFFFFFFFF, 2, 3] == [int(t["bank.seq"]) for t in ticks]
+    assert [int(t["trk.seq"]) for t in ticks] == [0xFFFFFFFF, 2, 3]
+    assert [(int(t["bank.count"]), int(t["bank.slot"]), int(t["lb.slot"]), int(t["f.full"])) for t in ticks] == \
+        [(1, 1, 0, 0), (2, 0, 1, 1), (2, 1, 0, 1)]
+    for a, b in zip(ticks, ticks[1:]):
+        assert a["trk.path_rd"] != a["trk.path_wr"] and a["trk.valid_rd"] != a["trk.valid_wr"]
+        assert (b["trk.path_rd"], b["trk.path_wr"]) == (a["trk.path_wr"], a["trk.path_rd"])
+        assert (b["trk.valid_rd"], b["trk.valid_wr"]) == (a["trk.valid_wr"], a["trk.valid_rd"])
+        assert a["trk.cost_wr"] != b["trk.cost_wr"] and a["trk.dbg"] == b["trk.dbg"]
+    assert [int(t["trk.path_ok"]) for t in ticks] == [0, 1, 1]
+    ex = prep(None, px=1, ticks=3, px_seq=0xFFFFFFFE)
+    assert [int(t["f.px_seq"]) for t in ex] == [0xFFFFFFFF, 2, 3] == [int(t["box.seq"]) for t in ex]
+    plain = prep(None, lb=0, ticks=3)
+    assert all(t["bank.seq"] == "7" and t["box.seq"] == "5" and t["bank.tseq"] == "11" for t in plain)
+
+
+def test_plan_track_layout(harness):
+    """d_trk: path copy 0 | path copy 1 | cost 0, cost 1 | the read-back: path | hp [HMAX][6] | theta [HMAX]
+    (kernels.hpp PlanTrack's dbg); d_trk_flags: valid 0, valid 1, the read-back's, the late word; d_hp_tag
+    [12 HMAX].  The regions are pairwise disjoint and inside their allocations, in that order; the largest
+    read-back copies (H = HMAX) end inside the buffer."""
+    L = parse_fields(harness("track_layout"))
+    assert (L["HMAX"], L["kPlanPathStride"], L["kPlanTrackDbgDoubles"]) == (HMAX, PATH_STRIDE, 2 * PATH_STRIDE + 7 * HMAX)
+    assert (L["row"], L["path_doubles"]) == (PATH_STRIDE, 2 * PATH_STRIDE)
+    regions = [("path0", L["path0"], L["path_doubles"]), ("path1", L["path1"], L["path_doubles"]), ("cost0", L["cost0"], 1),
+               ("cost1", L["cost1"], 1), ("rb_path", L["rb_path"], L["path_doubles"]), ("rb_hp", L["rb_hp"], 6 * HMAX),
+               ("rb_theta", L["rb_theta"], HMAX)]
+    end = 0
+    for name, off, size in regions:                      # in order, touching, none overlapping
+        assert off == end, (name, off, end)
+        end = off + size
+    assert end == L["trk_doubles"] == 4 * PATH_STRIDE + 2 + L["kPlanTrackDbgDoubles"]
+    assert L["rb_theta"] + HMAX - L["rb_path"] == L["kPlanTrackDbgDoubles"]
+    # the read-back's copies at H = HMAX: rows of H + 1 doubles at a stride of `row`, 6 H and H doubles
+    for base in (L["rb_path"], L["path0"], L["path1"]):
+        assert base + L["row"] + (HMAX + 1) <= base + L["path_doubles"] <= L["trk_doubles"]
+    assert L["rb_hp"] + 6 * HMAX <= L["rb_theta"] and L["rb_theta"] + HMAX <= L["trk_doubles"]
+    flags = [L["valid0"], L["valid1"], L["flag_rb_valid"], L["flag_late"]]
+    assert sorted(flags) == [0, 1, 2, 3] == list(range(L["flags"])) and flags == [0, 1, 2, 3]
+    assert L["hp_tag_words"] == 12 * HMAX
+
+
+E_ARG, E_STATE = -1, -4
+ASYNC = "an async tick is outstanding: call llampc_plan_wait"
+NO_TRACK = "no track set: call llampc_bank_set_track first"
+REFUSALS = [
+    # one bad field at a time: the plan input (the texts: capi.hip's check_plan_in)
+    (dict(null_in=1), E_ARG, "plan input is NULL"),
+    (dict(K=0), E_ARG, "K=0 outside [1, 32]"), (dict(K=33), E_ARG, "K=33 outside [1, 32]"),
+    (dict(no_prev=1), E_ARG, "look-back needs x_prev, u_prev and x_now"),
+    (dict(no_now=1), E_ARG, "look-back needs x_prev, u_prev and x_now"),
+    (dict(C=0), E_ARG, "C=0 H=3 must be >= 1"), (dict(H=0), E_ARG, "C=2 H=0 must be >= 1"),
+    (dict(C=8193, H=8192), E_ARG, "C*H too large"),
+    (dict(no_U=1), E_ARG, "look-ahead needs x_now, U, xref and uprev"),
+    (dict(no_now=1, lb=0), E_ARG, "look-ahead needs x_now, U, xref and uprev"),
+    (dict(integrator=3), E_ARG, "unknown integrator 3"), (dict(integrator=-1), E_ARG, "unknown integrator -1"),
+    (dict(xref_mode=2), E_ARG, "unknown xref_mode 2"),
+    (dict(xref_mode=XREF_RACELINE), E_STATE, "xref_mode RACELINE needs llampc_bank_set_raceline first"),
+    (dict(lb=0, la=0), E_ARG, "nothing to do: look-back and look-ahead both off"),
+    (dict(Ts=0), E_ARG, "Ts must be finite > 0"), (dict(Ts="nan"), E_ARG, "Ts must be finite > 0"),
+    (dict(Ts="inf"), E_ARG, "Ts must be finite > 0"), (dict(Ts=-0.02), E_ARG, "Ts must be finite > 0"),
+    # ... the corridor entries (check_corridor_mode: plan_shape's words; corridor_invalid's)
+    (dict(hp=1, la=0), E_ARG, NO["corridor_la"]), (dict(hp=1, integrator=RK6), E_ARG, NO["corridor_rk6"]),
+    (dict(hp=1, xref_mode=XREF_RACELINE, raceline=1), E_ARG, NO["corridor_raceline"]),
+    (dict(hp=1, weight=-1), E_ARG, "corridor: weight must be finite and >= 0"),
+    (dict(hp=1, weight="nan"), E_ARG, "corridor: weight must be finite and >= 0"),
+    (dict(hp=1, hp_bad=1), E_ARG, "corridor: a normal component is not finite"),
+    # ... the track entries (check_track_tick)
+    (dict(tt=1, tr_n=0), E_STATE, NO_TRACK), (dict(tt=1, **{"async": 1}), E_STATE, ASYNC),
+    (dict(tt=1, la=0), E_ARG, "the track tick's corridor belongs to the look-ahead: do_lookahead is 0"),
+    (dict(tt=1, integrator=RK6), E_ARG, "the track tick has no RK6 rollout"),
+    (dict(tt=1, integrator=EULER_NLP), E_ARG,
+     "the track tick has no NLP-Euler rollout (llampc_plan_corridor takes host-built rows)"),
+    (dict(tt=1, xref_mode=XREF_RACELINE, raceline=1), E_ARG, "the track tick takes the given xref only (not LLAMPC_XREF_RACELINE)"),
+    (dict(tt=1, tw=-1), E_ARG, "track tick: weight must be finite and >= 0"),
+    (dict(tt=1, tw="inf"), E_ARG, "track tick: weight must be finite and >= 0"),
+    (dict(tt=1, margin=1.2), E_ARG, "track tick: margin must be finite and below track_width / 2"),
+    (dict(tt=1, margin="nan"), E_ARG, "track tick: margin must be finite and below track_width / 2"),
+    (dict(tt=1, H=HMAX + 1), E_ARG, "H=65 above 64 (the path state's horizon)"),
+    # pairs: the order within an entry
+    (dict(tt=1, tr_n=0, tw=-1), E_STATE, NO_TRACK),                       # no track before a bad weight
+    (dict(tt=1, tr_n=0, **{"async": 1}), E_STATE, NO_TRACK),              # ... and before the outstanding tick
+    (dict(tt=1, integrator=RK6, **{"async": 1}), E_STATE, ASYNC),         # the outstanding tick before RK6
+    (dict(tt=1, integrator=RK6, tw=-1), E_ARG, "the track tick has no RK6 rollout"),
+    (dict(tt=1, tw=-1, K=0), E_ARG, "track tick: weight must be finite and >= 0"),
+    (dict(tt=1, null_in=1, tw=-1), E_ARG, "track tick: weight must be finite and >= 0"),
+    (dict(tt=1, null_in=1), E_ARG, "plan input is NULL"),
+    (dict(K=0, Ts=0), E_ARG, "K=0 outside [1, 32]"),                      # a bad K before a bad Ts
+    (dict(tt=1, K=0, H=HMAX + 1), E_ARG, "K=0 outside [1, 32]"),          # the plan input before the path's horizon
+    (dict(hp=1, integrator=RK6, K=0), E_ARG, NO["corridor_rk6"]),         # the corridor's modes before the plan input
+    (dict(hp=1, K=0, weight=-1), E_ARG, "K=0 outside [1, 32]"),           # ... its rows and weight after
+    (dict(hp=1, H=0, hp_bad=1), E_ARG, "C=2 H=0 must be >= 1"),
+    (dict(**{"async": 1}), 0, ""),                  # every other entry refuses it after the disarm, not here
+]
+
+
+@pytest.mark.parametrize("kw,code,msg", REFUSALS, ids=lambda v: "-".join(f"{k}{x}" for k, x in v.items()) if isinstance(v, dict) else None)
+def test_plan_entry_refusals(harness, kw, code, msg):
+    """Code and message of plan_entry_refused, one bad field at a time and in pairs that show the order.
+    ("n*C overflows" is not here: with n <= 2^31 - 1, llampc_bank_create's bound, and C <= 2^26 no input reaches it.)"""
+    out = harness("refuse", *(f"{k}={v}" for k, v in kw.items())).rstrip("\n")
+    got_code, _, got_msg = out.partition(" ")
+    assert (int(got_code), got_msg) == (code, msg)
+
+
+def test_plan_entries_accept(harness):
+    for kw in (dict(), dict(lb=0), dict(la=0), dict(hp=1), dict(tt=1), dict(tt=1, H=HMAX), dict(xref_mode=XREF_RACELINE, raceline=1),
+               dict(hp=1, integrator=EULER_NLP), dict(C=8192, H=8192), dict(tt=1, margin=-3.0), dict(tt=1, tw=0), dict(lb=0, no_prev=1)):
+        assert harness("refuse", *(f"{k}={v}" for k, v in kw.items())).strip() == "0", kw
