@@ -1,9 +1,10 @@
 // capi_common.hpp — what the C ABI's translation units share (capi.hip: errors, the bank's lifecycle,
 // the raceline upload; capi_plan.hip: the plan tick and its entries, the track entries; capi_batch.hip:
-// the raw batch calls and the merge; capi_xchg.hip: RCCL, mailboxes, exchange; capi_ctl.hip: the
-// controller; capi_nlp.hip: the NLP solver; capi_nlp_batch.hip: the batched NLP solver): error
-// reporting, the owners of device and pinned memory, the handle structs and the few functions one file
-// calls in another.  Nothing here is exported.
+// the raw batch calls and the merge; capi_xchg.hip: RCCL, mailboxes, exchange; capi_ctl.hip,
+// capi_ctl_shard.hip and capi_ctl_corr.hip over capi_ctl.hpp: the controller; capi_nlp.hip: the NLP
+// solver; capi_nlp_batch.hip: the batched NLP solver): error reporting, the owners of device and pinned
+// memory, the handle structs (the controller's: capi_ctl.hpp) and the few functions one file calls in
+// another.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 

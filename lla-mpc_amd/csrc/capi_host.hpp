@@ -1,7 +1,9 @@
 // capi_host.hpp — the C ABI's host arithmetic (capi*.hip): sequence numbers, poll bounds, the
 // input pack, the window unroll, the launch-argument fields that come from the bank, the plan tick's
-// prepare / commit, its track state's layout and its entries' refusals, and the controller launch's
-// shape (the plan launch's: launch_shape.hpp).  Pure: no HIP runtime call, so
+// prepare / commit, its track state's layout and its entries' refusals, the controller launch's shape
+// (the plan launch's: launch_shape.hpp), and the controller tick's prepare / commit, its speculative
+// look-ahead's decision, its corridor state's layout, its doorbell's words and its entries' refusals.
+// Pure: no HIP runtime call, so
 // tests/native/capi_host.cpp runs all of it on a machine with no GPU.
 #pragma once
 #include <algorithm>
@@ -769,14 +771,13 @@ inline int plan_entry_refused(const PlanBankFacts& b, const llampc_plan_in* in, 
     if (const char* why = corridor_invalid(hp, in->H, weight)) LLAMPC_REFUSE(LLAMPC_E_ARG, "corridor: %s", why);
   return LLAMPC_OK;
 }
-#undef LLAMPC_REFUSE
 
 // The launch shape of a controller tick (ctl.hip ctl_kernel<lpm, *>): the look-ahead's lanes per
 // rollout, lane group, candidates per lane and models per block, whether its input terms are
 // staged (s4: the staged layout fits the CU's 160 KiB and LLAMPC_CTL_NO_STAGE is off) and its
 // variates pre-drawn (zfit), the look-back's models per lane and the block counts, with the
 // launch's LDS bytes and the completing block's area offset.  The one statement of the rule: the
-// launch (capi_ctl.hip ctl_prepare) and llampc_ctl_variant both take it from here.
+// launch (ctl_tick_prepare below) and llampc_ctl_variant both take it from here.
 struct CtlShape {
   int lpm, G, cpl, mpb, s4, zfit, R, nb_lb, nb_la, nslots;
   size_t lds, poll_off;
@@ -817,6 +818,462 @@ inline CtlShape ctl_shape(int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl
   }
   return s;
 }
+
+// ---- the controller tick (capi_ctl.hip llampc_ctl_tick_async, ctl_arm) ----------------------------
+// The corridor tick's device state (ctl.hpp CtlCorridor), in the order it is allocated:
+//   d_cor       path copy 0 | path copy 1 (each [2][kCtlPathStride]) | read-back copy 0 | read-back copy 1,
+//               each path [2][kCtlPathStride] | hp [HMAX][6] | theta [HMAX] (kCtlCorDbgDoubles in all)
+//   d_cor_flag  valid 0, valid 1 | the read-backs' valid 0, valid 1
+//   d_hp_tag    [12 HMAX] tagged half-plane words
+// The one statement of it: the allocation, the launch arguments and the read-back take it here.
+struct CtlCorLayout {
+  size_t row = kCtlPathStride;           // a path's x row, then its y row
+  size_t path_doubles = 2 * row;         // one path copy
+  size_t rb_doubles = kCtlCorDbgDoubles; // one read-back copy: the path rows at 0, then
+  size_t rb_hp = path_doubles, rb_theta = rb_hp + 6 * LLAMPC_HMAX;
+  size_t cor_doubles = 2 * path_doubles + 2 * rb_doubles;
+  int flags = 4;
+  size_t hp_tag_words = 12 * (size_t)LLAMPC_HMAX;
+  constexpr size_t path(int r) const { return path_doubles * (size_t)r; }
+  constexpr size_t rb(int r) const { return 2 * path_doubles + rb_doubles * (size_t)r; }
+  constexpr int valid(int r) const { return r; }
+  constexpr int rb_valid(int r) const { return 2 + r; }
+};
+constexpr CtlCorLayout ctl_cor_layout() { return {}; }
+
+// An armed launch waits at most kArmBoundS for its doorbell; the host fires it only while it is
+// younger than kArmFreshS (else cancels it and launches the tick normally), so the launch cannot
+// expire between the host's check and its store short of a ~1 s stall of that thread.
+constexpr double kArmBoundS = 2.0;
+constexpr double kArmFreshS = 0.5;
+
+// What a tick takes from the controller, its bank and its transport, by address and constant
+// (capi_ctl.hpp ctl_view builds one per tick, on the stack).  mailbox false, xg_world 0, cor_w 0: no peer
+// exchange, no gather transport, no corridor — their fields are then not read.
+struct CtlView {
+  BankView bank;
+  const llampc_ctl_cfg* cfg;
+  CtlState* st;
+  llampc_ctl_out* out;                   // the device alias of the pinned record
+  uint64_t* host_tag;
+  uint64_t* sel_tag;  uint64_t* slot_tag;  unsigned* tickets;
+  double* dbg;  double* znoise;  uint64_t* ztag;
+  const double* pts;  const double* prefix;  int32_t np;
+  const uint64_t* door;  uint64_t* door_dev;
+  double* spec_val;  int64_t* spec_idx;  uint64_t* spec_tag;  uint64_t* spec_res;  uint64_t* xref_tag;
+  int32_t spec_nb, spec_cap;
+  bool no_spec, no_stage;
+  int32_t cus, share;                    // the bank's CU count (0: unknown) and concurrency
+  const double* rl_mus;                  // host: the raceline's mus [bank.rl_M]
+  const double* gparams;  int64_t n_global;          // the replicated global table (sharded)
+  bool mailbox;                          // the peer mailboxes: their table, world, rank and bound
+  uint64_t* const* px_box;
+  int32_t px_world, px_rank;
+  uint64_t px_bound;
+  int32_t xg_world, xg_rank;             // the gather transport and its two buffers
+  uint64_t* xsend;  const uint64_t* xgath;
+  const double* track;                   // cx | cy | tt, [3][tr_n]
+  int32_t tr_n;
+  double tr_L, tr_width;
+  double cor_w, cor_margin;              // the corridor's weight (0: off) and margin
+  double* cor;  int32_t* cor_flag;  uint64_t* hp_tag;   // ctl_cor_layout
+  double* cor_cost;
+};
+
+// The host state a tick reads and, once its launch was enqueued (or its armed launch rung), advances.
+struct CtlTickState {
+  int64_t t;                             // the tick's number
+  uint64_t hseq;                         // the completion tag's sequence
+  uint32_t seq, door_ctr;                // the launch tag's, the doorbell's (an armed prepare spends one)
+  int32_t hint_p0;                       // the state's projidx / mu-hat as the last record left them
+  double hint_mu;
+  bool cor_prev;                         // the last tick enqueued was a corridor tick
+  int32_t cor_nslots;
+  int32_t count, slot, W;                // the bank's window: rows filled, the row written next
+  uint32_t px_seq;                       // the transport's sequence: the mailbox's, or the gather's
+  bool px;                               // (a prepared next state) the tick exchanges: px_seq is committed
+};
+// A controller's, its bank's and (mb not null) its mailbox's state, and a prepared tick's next state
+// applied to them — all but door_ctr, which ctl_arm stores before its launch call: the number is spent
+// even if that call fails, and independently of the commit at the doorbell.  Templates only so that
+// the host harness runs them on plain structs of the same field names.
+template <class Ctl, class Bank, class Mailbox>
+inline CtlTickState ctl_tick_state(const Ctl& c, const Bank& b, const Mailbox* mb) {
+  return {c.t,      c.hseq,  c.seq, c.door_ctr, c.hint_p0, c.hint_mu, c.cor_prev, c.cor_nslots,
+          b.count,  b.slot,  b.W,   mb ? mb->seq : c.xg_seq, false};
+}
+template <class Ctl, class Bank, class Mailbox>
+inline void ctl_tick_commit(Ctl& c, Bank& b, Mailbox* mb, const CtlTickState& next) {
+  c.t = next.t;
+  c.hseq = next.hseq;
+  c.seq = next.seq;
+  c.cor_prev = next.cor_prev;
+  c.cor_nslots = next.cor_nslots;
+  b.count = next.count;
+  b.slot = next.slot;
+  if (next.px) {                         // committed after the launch was enqueued (next_seq)
+    if (mb) mb->seq = next.px_seq;
+    else c.xg_seq = next.px_seq;
+  }
+}
+
+// A prepared tick: its launch (ctl_kernel_corr with `cor` if corr, else ctl_kernel) and the state after it.
+struct CtlPrep {
+  bool corr = false;
+  CtlCorridor cor{};
+  CtlLaunch L{};
+  int lpm = 4;
+  size_t lds = 0;
+  CtlTickState next{};
+};
+
+// The speculative look-ahead's decision (CtlLaunch.n_spec): how many models an armed tick rolls out
+// before its doorbell, 0 for none.  Armed ticks past the warm-up whose rollouts are one model per block
+// in fused quads with diagonal Q / P (the spec blocks' layout), never with a gather transport; with the
+// peer mailboxes the ranks' lists are exchanged too (ctl.hip ctl_spec_exchange), in the slot after the
+// selection record's words, so they must fit there.  The armed footprint: every block of an armed
+// launch holds a CU from the end of the tick before to its doorbell, and all launches of the banks
+// ticked together (llampc_bank_set_concurrency) must be resident at once — the exchange's peers and the
+// tick's own look-back wait on each other — so the spec blocks take what is left of the banks' share of
+// the CUs (INTEGRATION.md "What armed launches cost").  lds / poll_off: the spec layout's, when > 0.
+struct CtlSpecIn {
+  bool armed, no_spec, warm, full, diag, mailbox;
+  int32_t R, s4, lpm, cpl, G, C, H, K, rl_n;
+  int32_t xg_world, px_G;
+  int32_t nb_lb, nb_la, spec_nb, spec_cap;
+  int32_t cus, share;
+  int64_t n;                             // the models the look-ahead can name: n_global with a mailbox
+};
+inline int32_t ctl_spec_models(const CtlSpecIn& s, size_t* lds, size_t* poll_off) {
+  const int cus = s.cus >= 1 ? s.cus : 256;
+  const int room = cus / std::max(1, s.share) - (s.nb_lb + s.nb_la);
+  const int ns = (int)std::min<int64_t>(std::min<int64_t>(s.spec_cap, room), s.n);
+  const bool px_fits = !s.mailbox || (s.px_G && ctl_rec_words(s.K) + 4 * ns <= kRecWords);
+  if (!(s.armed && !s.no_spec && !s.warm && s.full && s.R == 1 && s.s4 && s.lpm == 4 && s.cpl == 1 && s.G == s.C &&
+        s.diag && !s.xg_world && px_fits && ns >= 4 && s.nb_lb <= s.spec_nb))
+    return 0;
+  size_t poll_sp = 0;
+  const size_t lds_sp = ctl_lds_bytes(s.H, s.C, s.rl_n, s.nb_lb, s.K, &poll_sp, true, s.px_G, ns);
+  if (lds_sp > 160 * 1024) return 0;
+  *lds = lds_sp;
+  *poll_off = poll_sp;
+  return ns;
+}
+
+// The launch of tick st.t (x_t null: armed — the doorbell carries x_t) and the state after it, from the
+// view and the host's copy of the state (after ctl_refresh).  It refuses, with the message in buf, a
+// window that is not full after the warm-up and a launch above the CU's LDS.  An armed prepare takes
+// the next doorbell number: P.next.door_ctr holds it whatever is returned (st's own if the window was
+// refused), and ctl_arm stores it at once.
+inline int ctl_tick_prepare(const CtlView& v, const CtlTickState& st, const double* x_t, CtlPrep& P, char* buf,
+                            size_t nbuf) {
+  const BankView& bv = v.bank;
+  const llampc_ctl_cfg& k = *v.cfg;
+  const int64_t t = st.t;
+  const int32_t W = st.W;
+  const bool do_lb = t >= 2;             // rt.py:347 (the transition idt -> idt+1 from idt >= 1)
+  const bool warm = t <= W;              // rt.py:300-301
+  int32_t count = st.count;
+  if (do_lb) count = std::min(count + 1, W);
+  const bool full = do_lb && count >= W;
+  CtlTickState& nx = P.next = st;
+  if (!warm && !full)
+    LLAMPC_REFUSE(LLAMPC_E_STATE, "tick %lld: the look-back window is not full after the warm-up (was the bank reset?)",
+                  (long long)t);
+  CtlLaunch L{};
+  const int R = lookback_r(bv.n, k.K);
+  // look-back (rt.py:347-366 on the bank's ring)
+  bank_lookback(bv, L.lb);
+  L.lb.x_prev = v.st->x_prev;
+  L.lb.u_prev = v.st->u_prev;
+  L.lb.Ts = k.Ts;
+  L.lb.full = full;
+  L.lb.K = k.K;
+  L.lb.nan_first = k.nan_policy == LLAMPC_NAN_FIRST;
+  L.lb.R = R;
+  L.lb.wm_keep = 0;
+  // look-ahead constants (RK4 on the bank's vehicle, the NLP objective)
+  bank_lookahead(bv, LLAMPC_RK4, L.la);
+  L.la.C = k.C;
+  L.la.H = k.H;
+  L.la.Ts = k.Ts;
+  L.la.cost = make_cost(k.cost, k.Ts);
+  L.la.xref_mode = LLAMPC_XREF_GIVEN;
+  L.la.rl = raceline_view(bv);
+  L.la.rl.wcap = bv.rl_n - 1;
+  // lb_final's view
+  bank_final(bv, L.fin);
+  L.fin.out = &v.out->plan;
+  L.fin.do_lb = do_lb;
+  L.fin.do_la = 1;
+  L.fin.full = full;
+  L.fin.window_count = do_lb ? count : st.count;
+  L.fin.K = k.K;
+  L.fin.nan_first = k.nan_policy == LLAMPC_NAN_FIRST;
+  L.fin.nb_lb = do_lb ? lookback_blocks_r(bv.n, R) : 1;
+  L.fin.C = k.C;
+  // controller
+  nx.t = t + 1;
+  nx.hseq = st.hseq + 1;
+  nx.seq = next_seq(st.seq);
+  if (do_lb) {
+    nx.count = count;
+    nx.slot = (st.slot + 1) % W;
+  }
+  L.st = v.st;
+  L.out = v.out;
+  L.host_tag = v.host_tag;
+  L.host_seq = nx.hseq;
+  L.sel_tag = v.sel_tag;
+  L.slot_tag = v.slot_tag;
+  L.tickets = v.tickets;
+  L.dbg = v.dbg;
+  L.znoise = v.znoise;
+  L.ztag = v.ztag;
+  L.pts = v.pts;
+  L.prefix = v.prefix;
+  L.tick = (uint64_t)t;
+  L.seed = k.seed;
+  for (int j = 0; j < 6; ++j) {
+    L.x_t[j] = x_t ? x_t[j] : 0.0;      // armed (x_t null): the doorbell carries it
+    L.nominal[j] = k.nominal[j];
+  }
+  const double sqrt3 = std::sqrt(3.0);
+  for (int j = 0; j < 2; ++j) {
+    L.nscale[j] = sqrt3 * k.sigma[j];    // sqrt(3) sigma_j, one rounding (ctl.hpp ctl_cand_one)
+    L.rate[j] = k.cost.rate_max[j] < 0 ? -1.0 : k.cost.rate_max[j] * k.Ts;
+    L.umin[j] = k.cost.umin[j];
+    L.umax[j] = k.cost.umax[j];
+  }
+  L.mu_fixed = 1.0;                      // ConstantSpeed's defaults (rt.py:282)
+  L.scale_fixed = 1.0;
+  L.v_factor = k.v_factor;
+  L.mu_init = k.mu_init;
+  L.seq = nx.seq;
+  L.poll = (uint32_t)poll_units(poll_bound_ticks(bv.n, k.C, k.H), UINT32_MAX);
+  L.np = v.np;
+  L.lap_projidx = k.lap_projidx;
+  L.do_lb = do_lb;
+  L.warm = warm;
+  L.use_mu = t > W + 1;                  // rt.py:278
+  L.door_dev = v.door_dev;               // every launch: its x_t time (kCtlTimeWord)
+  if (!x_t) {                            // armed: the launch reads projidx / mu-hat from the state
+    L.door = v.door;
+    nx.door_ctr = st.door_ctr == 0xFFFFFFFFu ? 1u : st.door_ctr + 1u;   // never reused, never 0
+    L.door_seq = nx.door_ctr;
+    L.door_bound = (uint32_t)(kArmBoundS * 1e8 / 65536.0) + 1;
+  } else {                               // the last record's (ctl_refresh after a failed wait)
+    L.p0_walk = st.hint_p0;
+    L.br_walk = mu_bracket(v.rl_mus, bv.rl_M, L.use_mu ? st.hint_mu : L.mu_fixed);   // rt.py:278-282
+  }
+  L.full = full;
+  L.S = k.S;
+  L.K = k.K;
+  // sharded: the exchange runs on every tick whose window is full (the same ticks on every
+  // rank); the selection is global, the look-ahead reads the replicated global table
+  L.sel_goff = bv.goff;
+  if (v.mailbox || v.xg_world) {
+    L.la.params = v.gparams;
+    L.la.n = v.n_global;
+    L.la.goff = 0;
+    L.sel_goff = 0;
+  }
+  if (v.mailbox) {
+    if (full) {
+      nx.px = true;
+      nx.px_seq = next_seq(st.px_seq);
+      L.px_box = v.px_box;
+      L.px_G = v.px_world;
+      L.px_rank = v.px_rank;
+      L.px_seq = nx.px_seq;
+      L.px_bound = (uint32_t)poll_units(v.px_bound, UINT32_MAX);
+      L.poll = std::max(L.poll, L.px_bound);   // the look-ahead blocks wait for the merged selection
+    }
+  } else if (v.xg_world && full) {       // gather transport: two launches (CtlLaunch.px_phase; ctl_gather_split)
+    nx.px = true;
+    nx.px_seq = next_seq(st.px_seq);
+    L.px_G = v.xg_world;
+    L.px_rank = v.xg_rank;
+    L.px_seq = nx.px_seq;
+    L.px_phase = 1;
+    L.px_send = v.xsend;
+    L.px_gath = v.xgath;
+    L.px_bound = 16;                     // ~10 ms: the records are there when the launch starts
+  }
+  // the launch's shape (ctl_shape: the lane split, the staging, the block counts).  A corridor tick
+  // (llampc_ctl_set_corridor, weight > 0): ctl_kernel_corr — never staged, H corridor blocks, no
+  // speculative blocks (L.s4 = 0 rules them out)
+  const bool corr = v.cor_w > 0;
+  const CtlShape V = ctl_shape(bv.n, k.C, k.H, k.K, bv.rl_n, warm, do_lb, v.no_stage, L.px_G, corr ? v.tr_n : 0);
+  L.nslots = V.nslots;
+  L.G = V.G;
+  L.cpl = V.cpl;
+  L.mpb = V.mpb;
+  L.nb_lb = V.nb_lb;
+  L.nb_la = V.nb_la;
+  L.s4 = V.s4;
+  L.poll_off = V.poll_off;
+  size_t lds = V.lds;
+  if (lds > kCtlLdsMax) LLAMPC_REFUSE(LLAMPC_E_ARG, "controller tick needs %zu B of LDS (> 160 KiB)", lds);
+  {
+    const llampc_cost& cq = k.cost;
+    CtlSpecIn s{};
+    s.armed = !x_t, s.no_spec = v.no_spec, s.warm = warm, s.full = full, s.mailbox = v.mailbox;
+    s.diag = cq.Q[1] == 0.0 && cq.Q[2] == 0.0 && cq.P[1] == 0.0 && cq.P[2] == 0.0;
+    s.R = R, s.s4 = L.s4, s.lpm = V.lpm, s.cpl = L.cpl, s.G = L.G, s.C = k.C, s.H = k.H, s.K = k.K, s.rl_n = bv.rl_n;
+    s.xg_world = v.xg_world, s.px_G = L.px_G;
+    s.nb_lb = L.nb_lb, s.nb_la = L.nb_la, s.spec_nb = v.spec_nb, s.spec_cap = v.spec_cap;
+    s.cus = v.cus, s.share = v.share;
+    s.n = v.mailbox ? v.n_global : bv.n;
+    if (const int32_t ns = ctl_spec_models(s, &lds, &L.poll_off)) {
+      L.px_spec_off = ctl_rec_words(k.K);
+      L.px_spec_wait = 20000;            // 200 us: the ranks arm within microseconds of each other
+      L.n_spec = ns;
+      L.spec_val = v.spec_val;
+      L.spec_idx = v.spec_idx;
+      L.spec_tag = v.spec_tag;
+      L.spec_res = v.spec_res;
+      L.xref_tag = v.xref_tag;
+    }
+  }
+  lds = std::max<size_t>(lds, 82 * 1024); // one block per CU, as the plan launch (sc1 hand-offs)
+  P.corr = corr;
+  if (corr) {
+    // the path state and the read-back by tick parity (ctl.hpp CtlCorridor): tick t reads what tick
+    // t - 1 wrote and writes its own copy
+    constexpr CtlCorLayout Y = ctl_cor_layout();
+    CtlCorridor& q = P.cor;
+    const size_t tn = (size_t)v.tr_n;
+    const int wr = (int)(t & 1), rd = wr ^ 1;
+    q = CtlCorridor{};
+    q.trk = TrackK{v.track, v.track + tn, v.track + 2 * tn, v.tr_n, 0, v.tr_L};
+    q.hw = v.tr_width / 2 - v.cor_margin;
+    q.weight = v.cor_w;
+    q.hp_tag = v.hp_tag;
+    q.path_rd = v.cor + Y.path(rd);
+    q.path_wr = v.cor + Y.path(wr);
+    q.valid_rd = v.cor_flag + Y.valid(rd);
+    q.valid_wr = v.cor_flag + Y.valid(wr);
+    q.dbg = v.cor + Y.rb(wr);
+    q.dbg_valid = v.cor_flag + Y.rb_valid(wr);
+    q.path_ok = st.cor_prev ? 1 : 0;
+    q.dbg_cost = v.cor_cost;
+  }
+  nx.cor_prev = corr;
+  nx.cor_nslots = corr ? L.nslots : 0;
+  P.L = L;
+  P.lpm = V.lpm;
+  P.lds = lds;
+  return LLAMPC_OK;
+}
+
+// The gather transport's two launches from one prepared tick (CtlLaunch.px_phase 1): first the look-back
+// blocks alone, which leave this shard's record; after the gather, block 0 merges and completes beside
+// the look-ahead blocks.
+inline void ctl_gather_split(const CtlPrep& P, CtlPrep& first, CtlPrep& second) {
+  first = P;
+  first.L.nb_la = 0;
+  first.L.n_spec = 0;
+  second = P;
+  second.L.px_phase = 2;
+  second.L.nb_lb = 1;
+}
+
+// Whether an armed launch is rung (else cancelled, and the tick launched normally): it is fresh, it was
+// armed for this tick, and with the peer exchange its tick number is still the mailbox's next.
+inline bool ctl_arm_fires(double age_s, int64_t arm_t, int64_t t, int32_t arm_px_G, bool has_mailbox, uint32_t arm_px_seq,
+                          uint32_t mailbox_seq) {
+  const bool px_ok = !arm_px_G || !has_mailbox || arm_px_seq == next_seq(mailbox_seq);
+  return age_s < kArmFreshS && arm_t == t && px_ok;
+}
+
+// The doorbell's words (CtlLaunch.door): every word tagged door_seq in its high half — x_t as twelve
+// 32-bit halves (high, low), then the status.  Block 0 polls until all carry the tag, so the stores need
+// no order among themselves; the caller stores the last with release.
+inline void ctl_door_words(const double* x_t, uint32_t door_seq, uint64_t w[kCtlDoorWords]) {
+  const uint64_t tg = (uint64_t)door_seq << 32;
+  for (int j = 0; j < 6; ++j) {
+    uint64_t b;
+    std::memcpy(&b, &x_t[j], 8);
+    w[2 * j] = tg | (b >> 32);
+    w[2 * j + 1] = tg | (b & 0xFFFFFFFFull);
+  }
+  w[kCtlDoorWords - 1] = tg | kCtlDoorFire;
+}
+inline uint64_t ctl_door_cancel_word(uint32_t door_seq) { return ((uint64_t)door_seq << 32) | kCtlDoorCancel; }
+
+// ---- what the controller's entries refuse: LLAMPC_OK, or the code with the message in buf ---------
+// llampc_ctl_create (the lock-free part): the pointers, the cfg, the polyline, the bank's raceline and
+// the launch's LDS, in that order.
+inline int ctl_create_refused(bool out_null, bool arg_null, const llampc_ctl_cfg* cfg, int32_t np, int64_t n,
+                              bool raceline, int32_t rl_n, char* buf, size_t nbuf) {
+  if (out_null) LLAMPC_REFUSE(LLAMPC_E_ARG, "out is NULL");
+  if (arg_null || !cfg) LLAMPC_REFUSE(LLAMPC_E_ARG, "NULL argument");
+  const llampc_ctl_cfg& k = *cfg;
+  if (k.C < 1 || k.H < 1 || k.H > LLAMPC_HMAX || k.K < 1 || k.K > LLAMPC_KMAX)
+    LLAMPC_REFUSE(LLAMPC_E_ARG, "C=%d H=%d (1..%d) K=%d (1..%d)", k.C, k.H, LLAMPC_HMAX, k.K, LLAMPC_KMAX);
+  if (k.S < 1 || k.S > kCtlSMax) LLAMPC_REFUSE(LLAMPC_E_ARG, "S=%d outside [1, %d]", k.S, kCtlSMax);
+  if (!(k.Ts > 0) || !std::isfinite(k.Ts)) LLAMPC_REFUSE(LLAMPC_E_ARG, "Ts must be finite > 0");
+  if (np < 2) LLAMPC_REFUSE(LLAMPC_E_ARG, "np=%d < 2", np);
+  if (k.nan_policy != LLAMPC_NAN_FIRST && k.nan_policy != LLAMPC_NAN_IGNORE) LLAMPC_REFUSE(LLAMPC_E_ARG, "nan_policy");
+  if (!raceline) LLAMPC_REFUSE(LLAMPC_E_STATE, "the controller needs the bank's raceline (llampc_bank_set_raceline)");
+  size_t poll_off = 0;
+  const size_t lds = ctl_lds_bytes(k.H, k.C, rl_n, lookback_blocks_r(n, lookback_r(n, k.K)), k.K, &poll_off);
+  if (lds > 160 * 1024)
+    LLAMPC_REFUSE(LLAMPC_E_ARG, "controller tick needs %zu B of LDS (> 160 KiB): C*H=%d too large for this track", lds,
+                  k.C * k.H);
+  return LLAMPC_OK;
+}
+
+// llampc_ctl_set_corridor, after it cancelled an armed launch: the controller's state, then the weight
+// and margin, then (weight > 0) a corridor tick's LDS on the bank's shape.
+struct CtlCorridorFacts {
+  bool pending, sharded, no_stage;
+  int32_t tr_n;                          // 0: no track set
+  double tr_width;
+  int64_t n;
+  int32_t C, H, K, rl_n;
+};
+inline int ctl_corridor_refused(const CtlCorridorFacts& f, double weight, double margin, char* buf, size_t nbuf) {
+  if (f.pending) LLAMPC_REFUSE(LLAMPC_E_STATE, "a controller tick is outstanding");
+  if (!f.tr_n) LLAMPC_REFUSE(LLAMPC_E_STATE, "no track set: call llampc_ctl_set_track first");
+  if (f.sharded) LLAMPC_REFUSE(LLAMPC_E_STATE, "a sharded controller has no corridor ticks");
+  if (!(weight >= 0) || !std::isfinite(weight)) LLAMPC_REFUSE(LLAMPC_E_ARG, "weight must be finite and >= 0");
+  if (!std::isfinite(margin) || !(f.tr_width / 2 - margin > 0))
+    LLAMPC_REFUSE(LLAMPC_E_ARG, "margin %g leaves no corridor (track width %g)", margin, f.tr_width);
+  if (weight > 0) {
+    const CtlShape V = ctl_shape(f.n, f.C, f.H, f.K, f.rl_n, false, true, f.no_stage, 0, f.tr_n);
+    if (V.lds > kCtlLdsMax) LLAMPC_REFUSE(LLAMPC_E_ARG, "a corridor tick needs %zu B of LDS (> 160 KiB)", V.lds);
+  }
+  return LLAMPC_OK;
+}
+
+// llampc_ctl_variant (track_n null) and llampc_ctl_variant_corridor: the shape of a tick past the
+// warm-up (unsharded) into V, or why it has none.  C beyond kCtlVariantCMax: the candidates alone
+// (16 B each per step) exceed the CU's LDS, and the int products C * H stay far from overflow.
+constexpr int32_t kCtlVariantCMax = 1 << 16;
+inline int ctl_variant_refused(bool out_null, int64_t n, int32_t C, int32_t H, int32_t K, int32_t rl_n,
+                               const int32_t* track_n, bool no_stage, CtlShape& V, char* buf, size_t nbuf) {
+  if (out_null) LLAMPC_REFUSE(LLAMPC_E_ARG, "NULL argument");
+  const bool bad = n < 1 || C < 1 || C > kCtlVariantCMax || H < 1 || H > LLAMPC_HMAX || K < 1 || K > LLAMPC_KMAX || rl_n < 2;
+  if (!track_n) {
+    if (bad)
+      LLAMPC_REFUSE(LLAMPC_E_ARG, "n=%lld C=%d (1..%d) H=%d (1..%d) K=%d (1..%d) rl_n=%d", (long long)n, C, kCtlVariantCMax,
+                    H, LLAMPC_HMAX, K, LLAMPC_KMAX, rl_n);
+    V = ctl_shape(n, C, H, K, rl_n, false, true, no_stage, 0);
+    if (V.lds > kCtlLdsMax)              // llampc_ctl_create refuses the shape
+      LLAMPC_REFUSE(LLAMPC_E_ARG, "controller tick needs %zu B of LDS (> 160 KiB): C*H=%d too large for this track", V.lds,
+                    C * H);
+    return LLAMPC_OK;
+  }
+  if (bad || *track_n < 2 || *track_n > kTrackMaxPoints)
+    LLAMPC_REFUSE(LLAMPC_E_ARG, "n=%lld C=%d (1..%d) H=%d (1..%d) K=%d (1..%d) rl_n=%d track_n=%d (2..%d)", (long long)n, C,
+                  kCtlVariantCMax, H, LLAMPC_HMAX, K, LLAMPC_KMAX, rl_n, *track_n, kTrackMaxPoints);
+  V = ctl_shape(n, C, H, K, rl_n, false, true, false, 0, *track_n);
+  if (V.lds > kCtlLdsMax) LLAMPC_REFUSE(LLAMPC_E_ARG, "a corridor tick needs %zu B of LDS (> 160 KiB)", V.lds);
+  return LLAMPC_OK;
+}
+#undef LLAMPC_REFUSE
 
 // Spins until *tag == want (acquire): 0.  A tag that `stop` accepts ends the spin with
 // kSpinStopped.  After `bound`, on_timeout() runs once (it synchronises the stream, so a HIP

@@ -1,11 +1,14 @@
 """csrc/capi_host.hpp (the C ABI's pure host helpers: tick numbers, poll bounds, the input
 pack, the window unroll, the raceline view, the launch fields that come from the bank, the plan
-tick's prepare / commit, its track state's layout, its entries' refusals and the controller launch's
-shape) and csrc/launch_shape.hpp (the plan launch's shape) compiled for the
+tick's prepare / commit, its track state's layout, its entries' refusals, the controller launch's
+shape, and the controller tick's prepare / commit, speculative look-ahead decision, corridor layout,
+doorbell words and entries' refusals) and csrc/launch_shape.hpp (the plan launch's shape) compiled for the
 host with AddressSanitizer and UBSan and run on the CPU.  The harness (tests/native/capi_host.cpp)
 prints values; what they must be is worked out here."""
+import math
 import os
 import shutil
+import struct
 import subprocess
 
 import numpy as np
@@ -853,3 +856,502 @@ def test_plan_entries_accept(harness):
     for kw in (dict(), dict(lb=0), dict(la=0), dict(hp=1), dict(tt=1), dict(tt=1, H=HMAX), dict(xref_mode=XREF_RACELINE, raceline=1),
                dict(hp=1, integrator=EULER_NLP), dict(C=8192, H=8192), dict(tt=1, margin=-3.0), dict(tt=1, tw=0), dict(lb=0, no_prev=1)):
         assert harness("refuse", *(f"{k}={v}" for k, v in kw.items())).strip() == "0", kw
+
+
+# ---- the controller tick's host path (capi_host.hpp ctl_tick_prepare / ctl_tick_commit, ctl_spec_models, ----
+# ---- ctl_gather_split, ctl_cor_layout, the doorbell's words, ctl_arm_fires, the entries' refusals) ----------
+# The harness's `ctl_prep` mode runs controller ticks on a fake controller, bank and mailbox (fake_ctl_view:
+# fake_bank's addresses and 0x400000 on, never dereferenced; the mus a heap block of exactly rl_M doubles)
+# and prints every field of CtlLaunch, CtlCorridor, lpm, lds, the next state and the state after the
+# commit; ctl_model restates ctl.hpp's comments on the fields and rt.py's rule for the ticks.
+CV = dict(st=0x400000, out=0x401000, host_tag=0x402000, sel_tag=0x403000, slot_tag=0x404000, tickets=0x405000, dbg=0x406000,
+          znoise=0x407000, ztag=0x408000, pts=0x409000, prefix=0x409800, np=9, door=0x40A000, door_dev=0x40B000,
+          spec_val=0x40C000, spec_idx=0x40D000, spec_tag=0x40E000, spec_res=0x40F000, xref_tag=0x410000, gparams=0x411000,
+          px_box=0x412000, px_world=2, px_rank=1, px_bound=10 ** 9, xg_world=3, xg_rank=2, xsend=0x413000, xgath=0x414000,
+          track=0x420000, tr_n=4, tr_L=8.0, tr_width=2.4, cor=0x430000, cor_flag=0x440000, hp_tag=0x450000, cor_cost=0x460000,
+          mus=(0.5, 1.5), x_t=tuple(0.25 + j for j in range(6)), nominal=tuple(1.5 + j for j in range(6)), sigma=(0.1, 0.05),
+          seed=77, v_factor=0.9, mu_init=0.8, S=20, lap_projidx=7)
+CTL_DEFAULTS = dict(C=2, H=3, K=2, Ts=0.02, nan_policy=0, q1=0.0, transport="none", n_global=12, cor_w=0.0, cor_margin=0.05,
+                    spec_nb=1, spec_cap=32, no_spec=0, no_stage=0, cus=256, share=1, t=0, hseq=40, seq=7, door_ctr=3, hint_p0=5,
+                    hint_mu=0.75, cor_prev=0, count=0, slot=0, px_seq=5, kinds="l", reset=-1)
+CTL_PATH_STRIDE, CTL_COR_DBG = HMAX + 1, 2 * (HMAX + 1) + 7 * HMAX
+REC_WORDS = PLAN_OUT // 4                # kernels.hpp kRecWords: a mailbox slot's words per rank (372)
+E_WINDOW = "tick %d: the look-back window is not full after the warm-up (was the bank reset?)"
+
+
+def a16(x):
+    return (x + 15) & ~15
+
+
+def mu_bracket_model(mus, mu):
+    """raceline.hpp mu_bracket (planner.py:48-62): lo, hi, single, wa, wb, den."""
+    M = len(mus)
+    if mu < mus[0] or mu > mus[-1]:
+        i = M - 1 if mu > mus[-1] else 0
+        return i, i, 1, 1.0, 0.0, 1.0
+    hi = sum(1 for j in range(M - 1) if not mus[j] >= mu)
+    lo = M - 1 if hi == 0 else hi - 1
+    return lo, hi, 0, mus[hi] - mu, mu - mus[lo], mus[hi] - mus[lo]
+
+
+def ctl_off_model(H, C, rl_n, nb_lb, K, s4, px_G=0, n_spec=0, extra=0, role_min=0):
+    """ctl_lds.hpp ctl_lds_bytes' offset of the completing block's area: the largest of the look-ahead layout
+    (+ a corridor tick's extra, or another role's whole request), the exchange's region, lb_final's and the
+    speculative look-ahead's, 16-B aligned; the launch asks for 4 KiB more."""
+    end = max(a16(ctl_lds_model(H, C, rl_n, s4) + extra), role_min)
+    px = SCRATCH + a16(4 * px_G * 4 * (K + 1)) + 16 * px_G * K + 4 * KMAX + 16 if px_G else 0
+    spec = 0
+    if n_spec:
+        o = a16(SCRATCH + 16 * (H + 1))
+        o = a16(o + 16 * C * H)
+        o = a16(o + 16 * C * H + 16 * C)
+        o = a16(o + 16 * C * H) + 8 * 64 + 256
+        spec_px = a16(2 * ENT * nb_lb * n_spec) + a16(16 * px_G * n_spec) + 2 * ENT * px_G * n_spec if px_G else 0
+        spec = max(o, SCRATCH + max(12 * BLOCK, 2 * ENT * nb_lb * n_spec, spec_px))
+    return a16(max(end, px, lb_final_lds(nb_lb, K), spec))
+
+
+def spec_model(armed=1, no_spec=0, warm=0, full=1, diag=1, mailbox=0, R=1, s4=1, lpm=4, cpl=1, G=2, C=2, H=3, K=2, rl_n=5,
+               xg_world=0, px_G=0, nb_lb=1, nb_la=3, spec_nb=1, spec_cap=32, cus=256, share=1, n=5):
+    """ctl_spec_models: (n_spec, lds, poll_off); (0, None, None) when none."""
+    room = (cus if cus >= 1 else 256) // max(1, share) - (nb_lb + nb_la)
+    ns = min(spec_cap, room, n)
+    px_fits = not mailbox or (px_G and 4 * (K + 1) + 4 * ns <= REC_WORDS)
+    ok = (armed and not no_spec and not warm and full and R == 1 and s4 and lpm == 4 and cpl == 1 and G == C and diag
+          and not xg_world and px_fits and ns >= 4 and nb_lb <= spec_nb)
+    if not ok:
+        return 0, None, None
+    off = ctl_off_model(H, C, rl_n, nb_lb, K, True, px_G, ns)
+    return (ns, off + 4096, off) if off + 4096 <= 160 * KIB else (0, None, None)
+
+
+def ctl_model(env, **kw):
+    """[one dict per step of `kinds`] of every printed field."""
+    a = dict(CTL_DEFAULTS, **kw)
+    V, B, hx = CV, VIEW, (lambda p: format(p, "x"))
+    C, H, K, Ts, W, n, rl_n = a["C"], a["H"], a["K"], a["Ts"], VIEW["W"], VIEW["n"], VIEW["rl_n"]
+    mailbox, gather = a["transport"] == "mailbox", a["transport"] == "gather"
+    nan_first = int(a["nan_policy"] == 0)
+    c = dict(t=a["t"], hseq=a["hseq"], seq=a["seq"], door_ctr=a["door_ctr"], cor_prev=a["cor_prev"], cor_nslots=0, xg_seq=a["px_seq"])
+    bank, box = dict(count=a["count"], slot=a["slot"]), a["px_seq"]
+    poll0 = poll_model(n, C, H, max(0.0, float(env.get("LLAMPC_POLL_BOUND_S", 2.0))),
+                       max(0.0, float(env.get("LLAMPC_POLL_STEP_NS", 40.0))))[2]
+    m, xy = rl_n - 1, B["rl"] + 8 * rl_n
+    steps = []
+    for s, kind in enumerate(a["kinds"]):
+        if s == a["reset"]:
+            bank = dict(count=0, slot=0)
+        armed, t = kind != "l", c["t"]
+        st_px = box if mailbox else c["xg_seq"]
+        # rt.py:278-366: the look-back from the second transition on, the nominal model through tick W, the
+        # window full once W errors are in, mu-hat used from tick W + 2 on
+        do_lb, warm, use_mu = int(t >= 2), int(t <= W), int(t > W + 1)
+        count = min(bank["count"] + 1, W) if do_lb else bank["count"]
+        full = int(bool(do_lb) and count >= W)
+        o = {}
+        nx = dict(t=t, hseq=c["hseq"], seq=c["seq"], door_ctr=c["door_ctr"], hint_p0=a["hint_p0"], hint_mu=a["hint_mu"],
+                  cor_prev=c["cor_prev"], cor_nslots=c["cor_nslots"], count=bank["count"], slot=bank["slot"], W=W, px_seq=st_px, px=0)
+
+        def finish(rc, why=None):
+            o["rc"] = rc
+            if why is not None:
+                o["why"] = why
+            o.update({f"ctl.{k}": v for k, v in c.items()})
+            o.update({"bank.count": bank["count"], "bank.slot": bank["slot"], "box.seq": box})
+            steps.append(o)
+
+        if not warm and not full:
+            finish(E_STATE, E_WINDOW % t)
+            continue
+        nx.update(t=t + 1, hseq=c["hseq"] + 1, seq=next_seq(c["seq"]))
+        if do_lb:
+            nx.update(count=count, slot=(bank["slot"] + 1) % W)
+        if armed:
+            nx["door_ctr"] = 1 if c["door_ctr"] == 0xFFFFFFFF else c["door_ctr"] + 1
+            c["door_ctr"] = nx["door_ctr"]                      # ctl_arm stores it before its launch call
+        R = lookback_r(n, K)
+        corr = a["cor_w"] > 0
+        G = group(C)
+        lpm = 4 if 4 * G <= BLOCK else 2 if 2 * G <= BLOCK else 1
+        mpb, cpl = BLOCK // (G * lpm), cdiv(C, G)
+        nb_lb = cdiv(n, BLOCK * R) if do_lb else 1
+        nslots = 1 if warm else K + 1
+        nb_la = cdiv(nslots, mpb)
+        sharded = mailbox or gather
+        px_G = (V["px_world"] if mailbox else V["xg_world"]) if sharded and full else 0
+        if px_G:
+            nx.update(px=1, px_seq=next_seq(st_px))
+        if corr:
+            s4 = 0
+            off = ctl_off_model(H, C, rl_n, nb_lb, K, False, px_G, 0, 48 * H + 16 * (H + 1) + 16, 64 + 24 * V["tr_n"])
+        else:
+            off = ctl_off_model(H, C, rl_n, nb_lb, K, True, px_G)
+            s4 = int(not a["no_stage"] and off + 4096 <= 160 * KIB)
+            if not s4:
+                off = ctl_off_model(H, C, rl_n, nb_lb, K, False, px_G)
+        lds = off + 4096
+        n_spec, lds_sp, off_sp = spec_model(armed, a["no_spec"], warm, full, int(a["q1"] == 0.0), int(mailbox), R, s4, lpm, cpl, G, C,
+                                            H, K, rl_n, V["xg_world"] if gather else 0, px_G, nb_lb, nb_la, a["spec_nb"],
+                                            a["spec_cap"], a["cus"], a["share"], a["n_global"] if mailbox else n)
+        if n_spec:
+            lds, off = lds_sp, off_sp
+        lds = max(lds, ONE_BLOCK_PER_CU)
+        poll = poll0
+        px_bound = 0
+        if px_G:
+            px_bound = min(max((V["px_bound"] + 0xFFFF) >> 16, 1), UINT32_MAX) if mailbox else 16
+            if mailbox:
+                poll = max(poll, px_bound)
+        la_params, la_n, la_goff = (V["gparams"], a["n_global"], 0) if sharded else (B["params"], n, B["goff"])
+        br = (0, 0, 0, 0.0, 0.0, 0.0) if armed else mu_bracket_model(V["mus"], a["hint_mu"] if use_mu else 1.0)
+        L = {"lb.params": hx(B["params"]), "lb.n": n, "lb.goff": B["goff"], "lb.veh.lf": B["lf"], "lb.veh.mass": B["mass"],
+             "lb.x_prev": hx(V["st"]), "lb.u_prev": hx(V["st"] + 48), "lb.x_now": "0", "lb.Ts": Ts, "lb.ring": hx(B["ring"]),
+             "lb.W": W, "lb.slot": bank["slot"], "lb.full": full, "lb.K": K, "lb.nan_first": nan_first, "lb.R": R, "lb.wm_keep": 0,
+             "lb.err_out": "0", "lb.wm_buf": hx(B["wmean"]), "lb.am_val": hx(B["am_val"]), "lb.am_idx": hx(B["am_idx"]),
+             "lb.tk_val": hx(B["tk_val"]), "lb.tk_idx": hx(B["tk_idx"]),
+             "la.params": hx(la_params), "la.n": la_n, "la.goff": la_goff, "la.veh.lf": B["lf"], "la.veh.mass": B["mass"],
+             "la.veh.input_acc": 1, "la.veh.approx": 1, "la.x0": "0", "la.U": "0", "la.xref": "0", "la.uprev": "0", "la.C": C,
+             "la.H": H, "la.integrator": RK4, "la.Ts": Ts, "la.cost.umin0": -0.1, "la.cost.umin1": -0.35, "la.cost.umax0": 1.0,
+             "la.cost.umax1": 0.35, "la.cost.dmax0": -1.0, "la.cost.dmax1": 2.0 * Ts * (1.0 + 1e-9), "la.cost.enforce": 1,
+             "la.cost.pad": 0, "la.cost_out": "0", "la.best_cand": "0", "la.best_cost": "0", "la.pv": "0", "la.pidx": "0",
+             "la.pnf": "0", "la.xref_mode": XREF_GIVEN, "la.rl.knots": hx(B["rl"]), "la.rl.xy": hx(xy),
+             "la.rl.speed": hx(xy + 8 * 8 * m), "la.rl.mus": hx(xy + 8 * 8 * m + 8 * 4 * m * B["rl_M"]), "la.rl.n": rl_n,
+             "la.rl.M": B["rl_M"], "la.rl.wcap": rl_n - 1, "la.rl.hmin": B["rl_hmin"], "la.rl.vmax": B["rl_vmax"],
+             "la.xref_pm": "0", "la.la_tag": "0", "la.blk_tag": "0", "la.seq": 0, "la.poll": 0, "la.wq": "0",
+             "f.out": hx(V["out"]), "f.tickets": "0", "f.do_lb": do_lb, "f.do_la": 1, "f.full": full, "f.window_count": count,
+             "f.K": K, "f.nan_first": nan_first, "f.nb_lb": nb_lb, "f.nb_la": 0, "f.C": C, "f.current_model": 0, "f.n": n,
+             "f.goff": B["goff"], "f.params": hx(B["params"]), "f.best_cand": "0", "f.best_cost": "0", "f.am_val": hx(B["am_val"]),
+             "f.am_idx": hx(B["am_idx"]), "f.tk_val": hx(B["tk_val"]), "f.tk_idx": hx(B["tk_idx"]), "f.pv": "0", "f.pidx": "0",
+             "f.pnf": "0", "f.la_tag": "0", "f.blk_tag": "0", "f.seq": 0, "f.poll": 0, "f.host_tag": "0", "f.host_seq": 0,
+             "f.px_box": "0", "f.px_merged": "0", "f.px_G": 0, "f.px_rank": 0, "f.px_seq": 0, "f.px_bound": 0, "f.wq": "0",
+             "L.st": hx(V["st"]), "L.out": hx(V["out"]), "L.host_tag": hx(V["host_tag"]), "L.host_seq": nx["hseq"],
+             "L.sel_tag": hx(V["sel_tag"]), "L.slot_tag": hx(V["slot_tag"]), "L.tickets": hx(V["tickets"]), "L.dbg": hx(V["dbg"]),
+             "L.znoise": hx(V["znoise"]), "L.ztag": hx(V["ztag"]), "L.pts": hx(V["pts"]), "L.prefix": hx(V["prefix"]), "L.tick": t,
+             "L.seed": V["seed"], "L.mu_fixed": 1.0, "L.scale_fixed": 1.0, "L.v_factor": V["v_factor"], "L.mu_init": V["mu_init"],
+             "L.poll_off": off, "L.seq": nx["seq"], "L.poll": poll, "L.np": V["np"], "L.lap_projidx": V["lap_projidx"],
+             "L.do_lb": do_lb, "L.warm": warm, "L.use_mu": use_mu, "L.full": full, "L.nslots": nslots, "L.mpb": mpb, "L.G": G,
+             "L.cpl": cpl, "L.S": V["S"], "L.K": K, "L.nb_lb": nb_lb, "L.nb_la": nb_la, "L.s4": s4,
+             "L.p0_walk": 0 if armed else a["hint_p0"], "L.br.lo": br[0], "L.br.hi": br[1], "L.br.single": br[2], "L.br.wa": br[3],
+             "L.br.wb": br[4], "L.br.den": br[5], "L.sel_goff": 0 if sharded else B["goff"],
+             "L.px_box": hx(V["px_box"] if mailbox and px_G else 0), "L.px_G": px_G,
+             "L.px_rank": (V["px_rank"] if mailbox else V["xg_rank"]) if px_G else 0, "L.px_seq": nx["px_seq"] if px_G else 0,
+             "L.px_bound": px_bound, "L.px_phase": int(gather and bool(px_G)), "L.px_send": hx(V["xsend"] if gather and px_G else 0),
+             "L.px_gath": hx(V["xgath"] if gather and px_G else 0), "L.px_spec_off": 4 * (K + 1) if n_spec else 0,
+             "L.px_spec_wait": 20000 if n_spec else 0, "L.door": hx(V["door"] if armed else 0), "L.door_dev": hx(V["door_dev"]),
+             "L.door_seq": nx["door_ctr"] if armed else 0, "L.door_bound": int(2.0 * 1e8 / 65536.0) + 1 if armed else 0,
+             "L.n_spec": n_spec, "L.spec_val": hx(V["spec_val"] if n_spec else 0), "L.spec_idx": hx(V["spec_idx"] if n_spec else 0),
+             "L.spec_tag": hx(V["spec_tag"] if n_spec else 0), "L.spec_res": hx(V["spec_res"] if n_spec else 0),
+             "L.xref_tag": hx(V["xref_tag"] if n_spec else 0), "lpm": lpm, "lds": lds}
+        q = (1.0, a["q1"], 0.0, 4.0)
+        for i in range(4):
+            L.update({f"la.cost.Q{i}": q[i], f"la.cost.R{i}": 10.0 + i, f"la.cost.P{i}": (20.0 + i) if i in (0, 3) else 0.0})
+        for j in range(6):
+            L.update({f"L.x_t{j}": 0.0 if armed else V["x_t"][j], f"L.nominal{j}": V["nominal"][j]})
+        for j in range(2):
+            L.update({f"L.nscale{j}": math.sqrt(3.0) * V["sigma"][j], f"L.rate{j}": (-1.0, 2.0 * Ts)[j],
+                      f"L.umin{j}": (-0.1, -0.35)[j], f"L.umax{j}": (1.0, 0.35)[j]})
+        o.update(L)
+        o["corr"] = int(corr)
+        if corr:
+            wr = t & 1
+            rd = wr ^ 1
+            path = lambda r: V["cor"] + 8 * 2 * CTL_PATH_STRIDE * r
+            rb = lambda r: V["cor"] + 8 * (4 * CTL_PATH_STRIDE + CTL_COR_DBG * r)
+            o.update({"cor.cx": hx(V["track"]), "cor.cy": hx(V["track"] + 8 * V["tr_n"]), "cor.tt": hx(V["track"] + 16 * V["tr_n"]),
+                      "cor.n": V["tr_n"], "cor.npad": 0, "cor.L": V["tr_L"], "cor.hw": V["tr_width"] / 2 - a["cor_margin"],
+                      "cor.weight": a["cor_w"], "cor.hp_tag": hx(V["hp_tag"]), "cor.path_rd": hx(path(rd)), "cor.path_wr": hx(path(wr)),
+                      "cor.valid_rd": hx(V["cor_flag"] + 4 * rd), "cor.valid_wr": hx(V["cor_flag"] + 4 * wr), "cor.dbg": hx(rb(wr)),
+                      "cor.dbg_valid": hx(V["cor_flag"] + 4 * (2 + wr)), "cor.path_ok": int(bool(c["cor_prev"])), "cor.pad": 0,
+                      "cor.dbg_cost": hx(V["cor_cost"])})
+        if gather and px_G:
+            # the gather transport's two launches: the look-back blocks alone, then block 0 with the look-ahead blocks
+            o.update({f"s1.{k}": v for k, v in dict(L, **{"L.nb_la": 0, "L.n_spec": 0}).items()})
+            o.update({f"s2.{k}": v for k, v in dict(L, **{"L.px_phase": 2, "L.nb_lb": 1}).items()})
+        nx.update(cor_prev=int(corr), cor_nslots=nslots if corr else 0)
+        o.update({f"next.{k}": v for k, v in nx.items()})
+        if kind != "f":                  # the commit: everything but the doorbell number
+            c.update(t=nx["t"], hseq=nx["hseq"], seq=nx["seq"], cor_prev=nx["cor_prev"], cor_nslots=nx["cor_nslots"])
+            bank = dict(count=nx["count"], slot=nx["slot"])
+            if nx["px"]:
+                if mailbox:
+                    box = nx["px_seq"]
+                else:
+                    c["xg_seq"] = nx["px_seq"]
+        finish(0)
+    return steps
+
+
+@pytest.fixture(scope="module")
+def ctl_prep(harness):
+    """ctl_prep(env=None, **fields): the harness's steps, each checked against ctl_model field by field."""
+    def run(env=None, **fields):
+        out = harness("ctl_prep", *(f"{k}={v}" for k, v in fields.items()), env=env)
+        want = ctl_model(env or {}, **fields)
+        got = [dict() for _ in want]
+        for ln in out.strip().splitlines():
+            key, _, val = ln.partition(" ")
+            t, _, name = key.partition(".")
+            got[int(t[1:])][name] = val
+        for t, (g_, w_) in enumerate(zip(got, want)):
+            assert set(g_) == set(w_), (fields, t, sorted(set(g_) ^ set(w_)))
+            for k, w in w_.items():
+                ok = float(g_[k]) == w if isinstance(w, float) else g_[k] == str(w)
+                assert ok, (fields, t, k, g_[k], w)
+        return got
+    return run
+
+
+FULL = dict(t=5, count=3, slot=1)        # a tick past the warm-up on a full window: use_mu
+CTL_KINDS = {
+    "launched": dict(FULL),
+    "armed": dict(FULL, kinds="a"),                                    # the speculative look-ahead's five models
+    "armed_no_spec": dict(FULL, kinds="a", no_spec=1),
+    "armed_off_diagonal": dict(FULL, kinds="a", q1=0.5),
+    "warm_first": dict(t=0),
+    "warm_lookback": dict(t=2, count=0),
+    "unstaged": dict(FULL, no_stage=1),
+    "nan_ignore": dict(FULL, nan_policy=1),
+    "mailbox_full": dict(FULL, transport="mailbox"),
+    "mailbox_full_armed": dict(FULL, transport="mailbox", kinds="a"),
+    "mailbox_not_full": dict(t=2, count=0, transport="mailbox"),
+    "mailbox_not_full_armed": dict(t=2, count=0, transport="mailbox", kinds="a"),
+    "gather_full": dict(FULL, transport="gather"),                     # with both halves of ctl_gather_split
+    "gather_not_full": dict(t=3, count=1, transport="gather"),
+    "corridor_even": dict(FULL, t=6, cor_w=1e4, cor_prev=1),
+    "corridor_odd": dict(FULL, cor_w=1e4, cor_prev=1),
+    "corridor_even_first": dict(FULL, t=6, cor_w=1e4),
+    "corridor_odd_first": dict(FULL, cor_w=1e4, cor_margin=-0.5),
+    "corridor_armed": dict(FULL, cor_w=2.5, cor_prev=1, kinds="a"),
+    "corridor_warm": dict(t=1, cor_w=1e4),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(CTL_KINDS))
+def test_ctl_tick_prepare(ctl_prep, kind):
+    """Every field of CtlLaunch, CtlCorridor, lpm, lds and the next state for each kind of tick, and under
+    another poll bound."""
+    kw = CTL_KINDS[kind]
+    got = ctl_prep(None, **kw)[0]
+    ctl_prep({"LLAMPC_POLL_BOUND_S": "0.5"}, **kw)
+    assert got["rc"] == "0"
+    if kind == "armed":
+        assert (got["L.n_spec"], got["L.door_seq"], got["next.door_ctr"]) == ("5", "4", "4")
+    if kind in ("armed_no_spec", "armed_off_diagonal", "corridor_armed", "mailbox_not_full_armed"):
+        assert got["L.n_spec"] == "0" and got["L.door"] != "0"
+    if kind == "mailbox_full_armed":     # the ranks' lists in the slot after the selection record: 12 + 4 x 12 words
+        assert (got["L.n_spec"], got["L.px_spec_off"], got["L.px_seq"], got["next.px"]) == ("12", "12", "6", "1")
+    if kind == "gather_full":
+        assert (got["L.px_phase"], got["s1.L.px_phase"], got["s2.L.px_phase"]) == ("1", "1", "2")
+        assert (got["s1.L.nb_la"], got["s1.L.nb_lb"], got["s2.L.nb_la"], got["s2.L.nb_lb"]) == ("0", got["L.nb_lb"], got["L.nb_la"], "1")
+    if kind.startswith("corridor"):
+        assert got["L.s4"] == "0" and got["cor.path_rd"] != got["cor.path_wr"]
+        assert got["cor.path_ok"] == str(kw.get("cor_prev", 0)) and got["next.cor_prev"] == "1"
+
+
+def rt_rule(t, W):
+    """rt.py:278-366 per tick t on a window of W: (do_lb, warm, full, use_mu, window_count, slot after the tick)."""
+    errors = max(0, t - 1)               # the look-back runs from tick 2 on, one error per tick
+    return int(t >= 2), int(t <= W), int(errors >= W), int(t > W + 1), min(errors, W), errors % W
+
+
+def test_ctl_tick_chain(ctl_prep):
+    """t = 0 .. W + 3 chained through ctl_tick_commit, launched and armed: warm, look-back, full and use_mu ticks
+    by rt.py's rule; the sequences across 0xFFFFFFFF; the transport's sequence on full ticks only."""
+    W = VIEW["W"]
+    for kinds in ("l" * (W + 4), "laalala"):
+        for tr in ("none", "mailbox", "gather"):
+            if tr == "gather" and "a" in kinds:
+                continue                 # no armed launches over a gather transport (ctl_arm)
+            ticks = ctl_prep(None, kinds=kinds, transport=tr, seq=0xFFFFFFFD, door_ctr=0xFFFFFFFE, px_seq=0xFFFFFFFE)
+            px_seq, doors = 0xFFFFFFFE, []
+            for t, o in enumerate(ticks):
+                do_lb, warm, full, use_mu, wc, slot = rt_rule(t, W)
+                assert [int(o[k]) for k in ("L.do_lb", "L.warm", "L.full", "L.use_mu", "f.window_count", "bank.count", "bank.slot")] == \
+                    [do_lb, warm, full, use_mu, wc, wc, slot], (kinds, tr, t)
+                assert (int(o["L.tick"]), int(o["ctl.t"]), int(o["L.host_seq"])) == (t, t + 1, 41 + t)
+                assert int(o["L.nslots"]) == (1 if warm else 3) and int(o["lb.full"]) == int(o["f.full"]) == full
+                if tr != "none" and full:
+                    px_seq = next_seq(px_seq)
+                assert int(o["box.seq" if tr == "mailbox" else "ctl.xg_seq"]) == px_seq, (kinds, tr, t)
+                assert int(o["L.px_G"]) == (0 if tr == "none" or not full else 2 if tr == "mailbox" else 3)
+                if kinds[t] == "a":
+                    doors.append(int(o["L.door_seq"]))
+            assert [int(o["L.seq"]) for o in ticks] == [0xFFFFFFFE, 0xFFFFFFFF, 2, 3, 4, 5, 6]      # never 0, the next value 2
+            assert doors == [0xFFFFFFFF, 1, 2, 3][:len(doors)]                                     # never 0, the next value 1
+            assert int(ticks[-1]["ctl.door_ctr"]) == (doors[-1] if doors else 0xFFFFFFFE)
+            assert px_seq == (0xFFFFFFFE if tr == "none" else 3)                                    # 0xFFFFFFFF, 2, 3: three full ticks
+
+
+def test_ctl_tick_window_refused(ctl_prep):
+    """Past the warm-up a window that is not full is refused (LLAMPC_E_STATE) and nothing advances — not even
+    an armed prepare's doorbell number."""
+    for kind in "la":
+        ticks = ctl_prep(None, kinds="lllll" + kind + kind, reset=5, door_ctr=9)
+        for o in ticks[5:]:
+            assert (int(o["rc"]), o["why"]) == (E_STATE, E_WINDOW % 5)
+            assert (o["ctl.t"], o["ctl.hseq"], o["ctl.seq"], o["ctl.door_ctr"], o["bank.count"]) == ("5", "45", "12", "9", "0")
+    assert ctl_prep(None, t=4, count=1)[0]["rc"] == str(E_STATE)
+    assert ctl_prep(None, t=3, count=1)[0]["rc"] == "0"                  # the last warm tick may still be filling
+
+
+def test_ctl_armed_launch_failed(ctl_prep):
+    """An armed prepare whose launch call failed spends its doorbell number and nothing else; the next armed
+    prepare of the same tick takes the number after."""
+    a, b, c = ctl_prep(None, kinds="faa", transport="mailbox", **FULL)
+    assert (a["L.door_seq"], b["L.door_seq"], c["L.door_seq"]) == ("4", "5", "6")
+    assert (a["ctl.t"], a["ctl.hseq"], a["ctl.seq"], a["ctl.door_ctr"], a["bank.count"], a["bank.slot"], a["box.seq"]) == \
+        ("5", "40", "7", "4", "3", "1", "5")
+    same = lambda x, y: {k: v for k, v in x.items() if k.startswith(("L.", "lb.", "la.", "f.")) and x[k] != y[k]}
+    assert set(same(a, b)) == {"L.door_seq"}                             # the relaunch is the same tick
+    assert (b["ctl.t"], b["ctl.hseq"], b["ctl.seq"], b["box.seq"], b["bank.slot"]) == ("6", "41", "8", "6", "2")
+
+
+SPEC_ELIGIBLE = dict(armed=1, no_spec=0, warm=0, full=1, diag=1, mailbox=0, R=1, s4=1, lpm=4, cpl=1, G=2, C=2, xg_world=0, nb_lb=1,
+                     spec_nb=1, n=5)
+
+
+@pytest.fixture(scope="module")
+def ctl_spec(harness):
+    def run(**kw):
+        ns, lds, off = (int(x) for x in harness("ctl_spec", *(f"{k}={v}" for k, v in kw.items())).split())
+        want = spec_model(**kw)
+        assert (ns, lds, off) == (want[0], want[1] if want[0] else -1, want[2] if want[0] else -1), kw
+        return ns
+    return run
+
+
+def test_ctl_spec_models(ctl_spec):
+    """From an eligible tick every term flipped alone gives none; the room is cus / share less the tick's own
+    blocks; spec_cap, the models and the record's room with a mailbox bound it; fewer than four: none."""
+    assert ctl_spec(**SPEC_ELIGIBLE) == 5
+    for flip in (dict(armed=0), dict(no_spec=1), dict(warm=1), dict(full=0), dict(R=2), dict(s4=0), dict(lpm=2), dict(cpl=2),
+                 dict(G=4), dict(diag=0), dict(xg_world=2), dict(mailbox=1), dict(n=3), dict(nb_lb=2)):
+        assert ctl_spec(**dict(SPEC_ELIGIBLE, **flip)) == 0, flip
+    assert ctl_spec(**dict(SPEC_ELIGIBLE, mailbox=1, px_G=2, n=12)) == 12           # 12 + 4 x 12 words of 372
+    assert ctl_spec(**dict(SPEC_ELIGIBLE, mailbox=1, px_G=2, K=32, n=100, spec_cap=64)) == 0     # 132 + 256 > 372: not cut, none
+    assert ctl_spec(**dict(SPEC_ELIGIBLE, mailbox=1, px_G=2, K=32, n=100, spec_cap=60)) == 60    # 132 + 240 = 372
+    assert ctl_spec(**dict(SPEC_ELIGIBLE, nb_lb=2, spec_nb=2)) == 5
+    big = dict(SPEC_ELIGIBLE, n=10 ** 6, spec_cap=64, nb_lb=40, spec_nb=40, nb_la=11)
+    assert ctl_spec(**dict(big, cus=256, share=1)) == 64                              # room 205: the cap
+    assert ctl_spec(**dict(big, cus=256, share=2)) == 64                              # room 77
+    assert ctl_spec(**dict(big, cus=256, share=2, nb_la=50)) == 38                    # room 128 - 90 = 38, below the cap
+    assert ctl_spec(**dict(big, cus=256, share=4, nb_la=11)) == 13                    # 64 - 51
+    assert ctl_spec(**dict(big, cus=256, share=4, nb_la=21)) == 0                     # room 3
+    assert ctl_spec(**dict(big, cus=0, share=2, nb_la=50)) == 38                      # an unknown CU count reads as 256
+    assert ctl_spec(**dict(big, cus=104, share=0)) == 53                              # share below 1 reads as 1
+    assert ctl_spec(**dict(big, spec_cap=32)) == 32 and ctl_spec(**dict(big, spec_cap=3)) == 0
+    assert ctl_spec(**dict(SPEC_ELIGIBLE, n=4)) == 4 and ctl_spec(**dict(SPEC_ELIGIBLE, n=3)) == 0
+    # the spec layout's LDS: three [C][H] arrays of 16 B — 162 KiB at C H = 64 x 54, above the CU's 160
+    assert 3 * 16 * 64 * 53 <= 160 * KIB < 3 * 16 * 64 * 54
+    assert ctl_spec(**dict(SPEC_ELIGIBLE, G=64, C=64, H=54, rl_n=700)) == 0
+    assert ctl_spec(**dict(SPEC_ELIGIBLE, G=64, C=64, H=40, rl_n=700)) == 5
+
+
+def test_ctl_cor_layout(harness):
+    """d_cor: path copy 0 | path copy 1 | read-back copy 0 | read-back copy 1, a read-back copy being path rows |
+    hp [HMAX][6] | theta [HMAX] (ctl.hpp CtlCorridor's dbg); d_cor_flag: valid 0, valid 1, the read-backs' two;
+    d_hp_tag [12 HMAX].  In order, touching, inside their allocations; the inner offsets are the device's."""
+    L = parse_fields(harness("ctl_cor_layout"))
+    assert (L["HMAX"], L["kCtlPathStride"], L["kCtlCorDbgDoubles"]) == (HMAX, CTL_PATH_STRIDE, CTL_COR_DBG)
+    assert (L["row"], L["path_doubles"], L["rb_doubles"]) == (CTL_PATH_STRIDE, 2 * CTL_PATH_STRIDE, CTL_COR_DBG)
+    end = 0
+    for name, size in (("path0", L["path_doubles"]), ("path1", L["path_doubles"]), ("rb0", L["rb_doubles"]), ("rb1", L["rb_doubles"])):
+        assert L[name] == end, (name, L[name], end)
+        end += size
+    assert end == L["cor_doubles"] == 4 * CTL_PATH_STRIDE + 2 * CTL_COR_DBG
+    # inside a read-back copy: the device writes P at 0 (rows kCtlPathStride apart), hp at 2 kCtlPathStride, theta 6 HMAX on
+    assert (L["rb_hp"], L["rb_theta"]) == (2 * CTL_PATH_STRIDE, 2 * CTL_PATH_STRIDE + 6 * HMAX)
+    assert L["row"] + HMAX + 1 <= L["rb_hp"] and L["rb_hp"] + 6 * HMAX <= L["rb_theta"] and L["rb_theta"] + HMAX == L["rb_doubles"]
+    assert [L["valid0"], L["valid1"], L["rb_valid0"], L["rb_valid1"]] == [0, 1, 2, 3] == list(range(L["flags"]))
+    assert L["hp_tag_words"] == 12 * HMAX
+
+
+def test_ctl_door_words(harness):
+    """Twelve data words tag | high half, tag | low half of each x_t[j] (a NaN's payload and -0.0's sign kept),
+    then tag | fire; the cancel word; the fire rule one condition at a time."""
+    x = [1.5, -0.0, float.fromhex("0x1.fffffffffffffp+1023"), 5e-324, -2.75, 0.0]
+    bits = [struct.unpack("<Q", struct.pack("<d", v))[0] for v in x]
+    bits[3] = 0x7FF80000DEADBEEF         # a NaN with a payload
+    for seq in (1, 0x12345678, 0xFFFFFFFF):
+        out = harness("ctl_door", seq, *(hex(b) for b in bits)).split()
+        words, cancel, consts = [int(w, 16) for w in out[:13]], int(out[13], 16), out[14:]
+        fire_c, cancel_c = int(consts[0]), int(consts[1])
+        assert (fire_c, cancel_c, float(consts[2]), float(consts[3])) == (1, 2, 0.5, 2.0)
+        tag = seq << 32
+        want = [tag | h for b in bits for h in (b >> 32, b & 0xFFFFFFFF)] + [tag | fire_c]
+        assert words == want and cancel == tag | cancel_c
+    assert bits[1] == 1 << 63
+    fires = lambda age=0.1, arm_t=4, t=4, px_G=0, mb=0, arm_px=0, mb_seq=0: int(harness("ctl_fires", age, arm_t, t, px_G, mb, arm_px, mb_seq))
+    assert fires() == 1
+    assert fires(age=0.499) == 1 and fires(age=0.5) == 0 and fires(age=3.0) == 0        # fresh: younger than kArmFreshS
+    assert fires(arm_t=3) == 0 and fires(arm_t=5) == 0                                  # armed for another tick
+    assert fires(px_G=2, mb=1, arm_px=6, mb_seq=5) == 1                                 # the mailbox's next number
+    assert fires(px_G=2, mb=1, arm_px=6, mb_seq=6) == 0 and fires(px_G=2, mb=1, arm_px=6, mb_seq=4) == 0
+    assert fires(px_G=2, mb=1, arm_px=2, mb_seq=0xFFFFFFFF) == 1                        # across the wrap
+    assert fires(px_G=0, mb=1, arm_px=0, mb_seq=9) == 1                                 # no exchange on the armed tick
+    assert fires(px_G=2, mb=0, arm_px=6, mb_seq=9) == 1                                 # no mailbox
+
+
+LDS_CREATE = "controller tick needs %d B of LDS (> 160 KiB): C*H=%d too large for this track"
+VARIANT = "n=%d C=%d (1..65536) H=%d (1..64) K=%d (1..32) rl_n=%d"
+CTL_REFUSALS = [
+    # llampc_ctl_create
+    ("create", dict(out_null=1), E_ARG, "out is NULL"), ("create", dict(arg_null=1), E_ARG, "NULL argument"),
+    ("create", dict(null_cfg=1), E_ARG, "NULL argument"),
+    ("create", dict(C=0), E_ARG, "C=0 H=3 (1..64) K=2 (1..32)"), ("create", dict(H=0), E_ARG, "C=2 H=0 (1..64) K=2 (1..32)"),
+    ("create", dict(H=65), E_ARG, "C=2 H=65 (1..64) K=2 (1..32)"), ("create", dict(K=0), E_ARG, "C=2 H=3 (1..64) K=0 (1..32)"),
+    ("create", dict(K=33), E_ARG, "C=2 H=3 (1..64) K=33 (1..32)"),
+    ("create", dict(S=0), E_ARG, "S=0 outside [1, 64]"), ("create", dict(S=65), E_ARG, "S=65 outside [1, 64]"),
+    ("create", dict(Ts=0), E_ARG, "Ts must be finite > 0"), ("create", dict(Ts="nan"), E_ARG, "Ts must be finite > 0"),
+    ("create", dict(Ts="inf"), E_ARG, "Ts must be finite > 0"), ("create", dict(np=1), E_ARG, "np=1 < 2"),
+    ("create", dict(nan_policy=2), E_ARG, "nan_policy"),
+    ("create", dict(raceline=0), E_STATE, "the controller needs the bank's raceline (llampc_bank_set_raceline)"),
+    ("create", dict(C=300, H=40, rl_n=700), E_ARG, LDS_CREATE % (ctl_off_model(40, 300, 700, 1, 2, False) + 4096, 12000)),
+    ("create", dict(out_null=1, arg_null=1), E_ARG, "out is NULL"), ("create", dict(arg_null=1, C=0), E_ARG, "NULL argument"),
+    ("create", dict(C=0, S=0), E_ARG, "C=0 H=3 (1..64) K=2 (1..32)"), ("create", dict(S=0, Ts=0), E_ARG, "S=0 outside [1, 64]"),
+    ("create", dict(Ts=0, np=1), E_ARG, "Ts must be finite > 0"), ("create", dict(np=1, nan_policy=2), E_ARG, "np=1 < 2"),
+    ("create", dict(nan_policy=2, raceline=0), E_ARG, "nan_policy"),
+    ("create", dict(raceline=0, C=300, H=40, rl_n=700), E_STATE, "the controller needs the bank's raceline (llampc_bank_set_raceline)"),
+    ("create", dict(), 0, ""), ("create", dict(C=64, H=40, K=32, S=64, np=2, nan_policy=1, rl_n=700), 0, ""),
+    # llampc_ctl_set_corridor
+    ("corridor", dict(pending=1), E_STATE, "a controller tick is outstanding"),
+    ("corridor", dict(tr_n=0), E_STATE, "no track set: call llampc_ctl_set_track first"),
+    ("corridor", dict(sharded=1), E_STATE, "a sharded controller has no corridor ticks"),
+    ("corridor", dict(weight=-1), E_ARG, "weight must be finite and >= 0"), ("corridor", dict(weight="nan"), E_ARG, "weight must be finite and >= 0"),
+    ("corridor", dict(weight="inf"), E_ARG, "weight must be finite and >= 0"),
+    ("corridor", dict(margin=1.2), E_ARG, "margin 1.2 leaves no corridor (track width 2.4)"),
+    ("corridor", dict(margin="nan"), E_ARG, "margin nan leaves no corridor (track width 2.4)"),
+    ("corridor", dict(C=300, H=40, rl_n=700), E_ARG, "a corridor tick needs %d B of LDS (> 160 KiB)" %
+     (ctl_off_model(40, 300, 700, 1, 2, False, 0, 0, 48 * 40 + 16 * 41 + 16, 64 + 24 * 4) + 4096)),
+    ("corridor", dict(pending=1, tr_n=0), E_STATE, "a controller tick is outstanding"),
+    ("corridor", dict(tr_n=0, sharded=1), E_STATE, "no track set: call llampc_ctl_set_track first"),
+    ("corridor", dict(sharded=1, weight=-1), E_STATE, "a sharded controller has no corridor ticks"),
+    ("corridor", dict(weight=-1, margin=1.2), E_ARG, "weight must be finite and >= 0"),
+    ("corridor", dict(margin=1.2, C=300, H=40, rl_n=700), E_ARG, "margin 1.2 leaves no corridor (track width 2.4)"),
+    ("corridor", dict(weight=0, C=300, H=40, rl_n=700), 0, ""),                    # off: no shape to refuse
+    ("corridor", dict(), 0, ""), ("corridor", dict(margin=-3.0), 0, ""), ("corridor", dict(weight=0), 0, ""),
+    # llampc_ctl_variant and llampc_ctl_variant_corridor
+    ("variant", dict(out_null=1), E_ARG, "NULL argument"), ("variant", dict(out_null=1, track_n=4), E_ARG, "NULL argument"),
+    ("variant", dict(n=0), E_ARG, VARIANT % (0, 2, 3, 2, 5)), ("variant", dict(C=0), E_ARG, VARIANT % (5, 0, 3, 2, 5)),
+    ("variant", dict(C=65537), E_ARG, VARIANT % (5, 65537, 3, 2, 5)), ("variant", dict(H=65), E_ARG, VARIANT % (5, 2, 65, 2, 5)),
+    ("variant", dict(K=33), E_ARG, VARIANT % (5, 2, 3, 33, 5)), ("variant", dict(rl_n=1), E_ARG, VARIANT % (5, 2, 3, 2, 1)),
+    ("variant", dict(C=65537, track_n=4), E_ARG, VARIANT % (5, 65537, 3, 2, 5) + " track_n=4 (2..4096)"),
+    ("variant", dict(track_n=1), E_ARG, VARIANT % (5, 2, 3, 2, 5) + " track_n=1 (2..4096)"),
+    ("variant", dict(track_n=4097), E_ARG, VARIANT % (5, 2, 3, 2, 5) + " track_n=4097 (2..4096)"),
+    ("variant", dict(C=300, H=40, rl_n=700), E_ARG, LDS_CREATE % (ctl_off_model(40, 300, 700, 1, 2, False) + 4096, 12000)),
+    ("variant", dict(C=300, H=40, rl_n=700, track_n=4), E_ARG, "a corridor tick needs %d B of LDS (> 160 KiB)" %
+     (ctl_off_model(40, 300, 700, 1, 2, False, 0, 0, 48 * 40 + 16 * 41 + 16, 64 + 24 * 4) + 4096)),
+    ("variant", dict(out_null=1, n=0), E_ARG, "NULL argument"), ("variant", dict(n=0, C=300, H=40, rl_n=700), E_ARG, VARIANT % (0, 300, 40, 2, 700)),
+    ("variant", dict(C=65536, H=1, rl_n=2), E_ARG, LDS_CREATE % (ctl_off_model(1, 65536, 2, 1, 2, False) + 4096, 65536)),
+    ("variant", dict(), 0, "lpm=4 nb_cor=0"), ("variant", dict(track_n=4), 0, "lpm=4 nb_cor=3"), ("variant", dict(track_n=4096, C=130), 0, "lpm=1 nb_cor=3"),
+]
+
+
+@pytest.mark.parametrize("entry,kw,code,msg", CTL_REFUSALS,
+                         ids=lambda v: "-".join(f"{k}{x}" for k, x in v.items()) if isinstance(v, dict) else v if isinstance(v, str) and " " not in v else None)
+def test_ctl_entry_refusals(harness, entry, kw, code, msg):
+    """Code and message of ctl_create_refused, ctl_corridor_refused and ctl_variant_refused (one
+    kCtlVariantCMax), one bad field at a time and in pairs that show each entry's order."""
+    out = harness("ctl_refuse", entry, *(f"{k}={v}" for k, v in kw.items())).rstrip("\n")
+    got_code, _, got_msg = out.partition(" ")
+    assert (int(got_code), got_msg) == (code, msg)
