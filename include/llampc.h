@@ -138,7 +138,9 @@ typedef struct llampc_plan_out {
   int32_t sel_cand;       /* argmin_c cost[sel_model, c]  ("chosen control")       */
   int32_t n_nonfinite;    /* look-ahead rollouts whose cost is not finite          */
   double  sel_cost;
-  int64_t la_best_model;  /* argmin over all (model, candidate) costs              */
+  int64_t la_best_model;  /* argmin over all (model, candidate) costs, NaN as +inf;
+                             -1 (with la_best_cand -1, la_best_cost NaN) without a
+                             look-ahead and when every cost of the tick is NaN     */
   int32_t la_best_cand;
   int32_t status;         /* 0 ok; LLAMPC_STATUS_POLL_TIMEOUT (1): the in-launch
                              completion (or the peer exchange) gave up waiting (a device
@@ -220,7 +222,8 @@ int llampc_lookback(llampc_bank* bank, const double* x_prev, const double* u_pre
  * cost.enforce_bounds costs +inf; the argmins treat NaN as +inf and break ties towards the
  * lower index, so when every candidate of a model is infeasible its best candidate is 0 with
  * cost +inf, and when every (model, candidate) pair is, best_model = best_cand = 0 and
- * best_cost = +inf (np.argmin over all-inf). */
+ * best_cost = +inf (np.argmin over all-inf).  When every cost is NaN there is no best:
+ * best_model = best_cand = -1, best_cost = NaN (the record's la_best_*). */
 int llampc_lookahead(llampc_bank* bank, const double* x0, const double* U, int32_t C,
                      int32_t H, const double* xref, const double* uprev,
                      const llampc_cost* cost, double Ts, int32_t integrator,

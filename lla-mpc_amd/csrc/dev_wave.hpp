@@ -11,6 +11,26 @@
 
 namespace llampc {
 
+// split_key's arithmetic (below), callable from the host: key = m C + c with 0 <= c < C for
+// 0 <= key < 2^63, 1 <= C < 2^31.  The fp64 quotient of the key is within 2^11 of m (the key's
+// rounding to 53 bits over C >= 1), the quotient of that step's exact remainder within 1 of the
+// rest, and one fix-up step makes the split exact (tests/test_split_key.py checks it against / and %).
+__host__ __device__ __forceinline__ void split_key_hd(int64_t key, int32_t C, int64_t& m, int32_t& c) {
+  const double dc = (double)C;
+  int64_t q = (int64_t)((double)key / dc);
+  q += (int64_t)((double)(key - q * C) / dc);
+  int64_t r = key - q * C;
+  if (r < 0) {
+    q -= 1;
+    r += C;
+  } else if (r >= C) {
+    q += 1;
+    r -= C;
+  }
+  m = q;
+  c = (int32_t)r;
+}
+
 namespace {
 
 template <int NAN_FIRST>
@@ -152,23 +172,10 @@ __device__ __forceinline__ T ld_wt(const T* p) {
 }
 
 // key = m C + c (0 <= c < C, 0 <= key < 2^63) split without the 64-bit integer division's
-// ~150-instruction software sequence (the controller record's look-ahead best): the fp64
-// quotient of the key is within 2^11 of m (the key's rounding), that of the exact remainder
-// within 1, and one fix-up step makes the split exact.
+// ~150-instruction software sequence (the controller record's and the plan record's look-ahead
+// best): split_key_hd above.
 __device__ __forceinline__ void split_key(int64_t key, int32_t C, int64_t& m, int32_t& c) {
-  const double dc = (double)C;
-  int64_t q = (int64_t)((double)key / dc);
-  q += (int64_t)((double)(key - q * C) / dc);
-  int64_t r = key - q * C;
-  if (r < 0) {
-    q -= 1;
-    r += C;
-  } else if (r >= C) {
-    q += 1;
-    r -= C;
-  }
-  m = q;
-  c = (int32_t)r;
+  split_key_hd(key, C, m, c);
 }
 
 // Tagged 64-bit words of the polled completion: launch tag in the high half, payload low.

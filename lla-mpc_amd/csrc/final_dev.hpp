@@ -255,6 +255,23 @@ __device__ __forceinline__ void final_write(const FinalLaunch& f, bool lb, int64
   const int tid = threadIdx.x;
   llampc_plan_out* o = f.out;
   const double nan = __builtin_nan("");
+  // The look-ahead best's (model, candidate) from its key (goff + n) C + c, ahead of the stores (none
+  // of them waits for it): at C = 1 the key is the model; else split_key, not the 64-bit / and %, whose
+  // ~150-instruction software sequence is one lane's dependent chain between the poll and the record.
+  // No look-ahead best (-1, -1, NaN) without a look-ahead, without a key, and when the best cost is NaN:
+  // the picks order NaN last, so lav is NaN only if every (model, candidate) cost of the tick is.  (+inf
+  // is a cost: every pair infeasible still gives (0, 0, +inf), llampc.h.)
+  const bool la_ok = f.do_la && lai != kNoIndex && lav == lav;
+  int64_t lam = -1;
+  int32_t lac = -1;
+  if (la_ok) {
+    if (f.C == 1) {
+      lam = lai;
+      lac = 0;
+    } else {
+      split_key(lai, f.C, lam, lac);
+    }
+  }
   // sc1 stores like lb_final's: the fused peer exchange reads the whole record back sc1
   if (tid < LLAMPC_KMAX) {
     const int k = tid;
@@ -281,9 +298,8 @@ __device__ __forceinline__ void final_write(const FinalLaunch& f, bool lb, int64
     st_wt(&o->sel_owned, (int32_t)owned);
     st_wt(&o->sel_cand, scand);
     st_wt(&o->sel_cost, scost);
-    const bool la_ok = f.do_la && lai != kNoIndex;
-    st_wt(&o->la_best_model, la_ok ? lai / f.C : (int64_t)-1);
-    st_wt(&o->la_best_cand, la_ok ? (int32_t)(lai % f.C) : (int32_t)-1);
+    st_wt(&o->la_best_model, lam);
+    st_wt(&o->la_best_cand, lac);
     st_wt(&o->la_best_cost, la_ok ? lav : nan);
     __hip_atomic_store(&f.tickets[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&f.tickets[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -36,7 +36,9 @@ __device__ __forceinline__ void la_publish(const LookaheadLaunch& a, int blk, co
     sc.sn[threadIdx.x >> 6] = nfw;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
+  // polled: lanes 0..4 of the first wave all fold the waves' picks (broadcast LDS reads; the pick left
+  // wave 0's in every lane) and lane w stores tagged word w — one store instruction, not five in turn
+  if (threadIdx.x < 5) {
     int nfs = sc.sn[0];
 #pragma unroll
     for (int w = 1; w < NW; ++w) {
@@ -48,12 +50,14 @@ __device__ __forceinline__ void la_publish(const LookaheadLaunch& a, int blk, co
     if (a.poll) {
       uint64_t* r = a.blk_tag + 5 * (int64_t)blk;
       const uint64_t vb = (uint64_t)__double_as_longlong(v), kb = (uint64_t)key;
-      st_wt(&r[0], tag_word(a.seq, (uint32_t)(vb >> 32)));
-      st_wt(&r[1], tag_word(a.seq, (uint32_t)vb));
-      st_wt(&r[2], tag_word(a.seq, (uint32_t)(kb >> 32)));
-      st_wt(&r[3], tag_word(a.seq, (uint32_t)kb));
-      st_wt(&r[4], tag_word(a.seq, (uint32_t)nfs));
-    } else {
+      const int w = threadIdx.x;
+      uint32_t p = (uint32_t)(vb >> 32);
+      p = w == 1 ? (uint32_t)vb : p;
+      p = w == 2 ? (uint32_t)(kb >> 32) : p;
+      p = w == 3 ? (uint32_t)kb : p;
+      p = w == 4 ? (uint32_t)nfs : p;
+      st_wt(&r[w], tag_word(a.seq, p));
+    } else if (threadIdx.x == 0) {
       st_wt(&a.pv[blk], v);
       st_wt(&a.pidx[blk], key);
       st_wt(&a.pnf[blk], nfs);
@@ -620,8 +624,9 @@ __device__ __forceinline__ void lookahead_block(const LookaheadLaunch& a, int bl
     }
   }
   if (live && g == 0 && sub == 0) {
-    if (a.poll) {                       // tagged words only (SoA: coalesced rows); C = 1: the
-      // candidate is 0, so only the cost's two words (final_poll)
+    if (a.poll) {                       // tagged words only (SoA: coalesced rows).  All three at C = 1
+      // too, where the candidate is 0: leaving the third out (and final_poll not waiting for it) did not
+      // make the tick faster (DESIGN.md §3 "Round 13")
       st_wt(&a.la_tag[n], tag_word(a.seq, (uint32_t)(__double_as_longlong(bv) >> 32)));
       st_wt(&a.la_tag[a.n + n], tag_word(a.seq, (uint32_t)__double_as_longlong(bv)));
       st_wt(&a.la_tag[2 * a.n + n], tag_word(a.seq, (uint32_t)(int32_t)bc));
