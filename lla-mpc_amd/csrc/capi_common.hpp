@@ -126,6 +126,30 @@ struct MappedRecord {
   }
 };
 
+// A track's centre-line tables on the device, cx | cy | tt, [3][n], with its closed length and width
+// (llampc_*_set_track): the bank's, the controller's and the two NLP solvers' each own one.
+struct TrackTables {
+  DevBuf<double> d;
+  int32_t n = 0;                         // 0: no track set
+  double L = 0.0, width = 0.0;
+  // Replaces the tables with ones track_tables_invalid accepts, once `s` has drained (no launch reads the
+  // tables being replaced); the caller holds the owner's locks, its device current.  A failure leaves no track.
+  int upload(hipStream_t s, const double* centre, const double* theta, int32_t n_, double L_, double width_) {
+    HIP_TRY(hipStreamSynchronize(s));
+    n = 0;
+    if (int rc = d.reserve(3 * (size_t)n_, 0, "track tables")) return rc;
+    std::vector<double> h(3 * (size_t)n_);
+    std::memcpy(h.data(), centre, 2 * (size_t)n_ * sizeof(double));
+    std::memcpy(h.data() + 2 * (size_t)n_, theta, (size_t)n_ * sizeof(double));
+    HIP_TRY(hipMemcpy(d.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    n = n_;
+    L = L_;
+    width = width_;
+    return LLAMPC_OK;
+  }
+  llampc::TrackK view() const { return {d.get(), d.get() + n, d.get() + 2 * (size_t)n, n, 0, L}; }
+};
+
 // ---- peer exchange (xGMI mailboxes; capi_xchg.hip) -------------------------------------
 struct llampc_mailbox {
   int32_t world = 0, rank = 0, device = 0;
@@ -202,9 +226,7 @@ struct llampc_bank {
   // every other call that enqueues on the stream cancels it first (bank_disarm)
   llampc_ctl* armed = nullptr;
   // the track tick (llampc_plan_track; kernels.hpp PlanTrack)
-  DevBuf<double> d_track;                // llampc_bank_set_track: cx | cy | tt, [3][tr_n]
-  int32_t tr_n = 0;                      // 0: no track set
-  double tr_L = 0.0, tr_width = 0.0;
+  TrackTables track;                     // llampc_bank_set_track
   DevBuf<double> d_trk;                  // the path copies [2][2][HMAX + 1] | their costs [2] | the read-back
   DevBuf<int32_t> d_trk_flags;           // the copies' valid flags [2] | the read-back's | the late word
   DevBuf<uint64_t> d_hp_tag;             // [12 HMAX] tagged half-plane words
@@ -222,13 +244,25 @@ static inline llampc::BankView bank_view(const llampc_bank& b) {
 static inline llampc::PlanView plan_view(const llampc_bank& b, const llampc_mailbox* px) {
   return {bank_view(b), b.d_best_cand.get(), b.d_best_cost.get(), b.d_pv.get(), b.d_pidx.get(), b.d_pnf.get(),
           b.d_la_tag.get(), b.d_blk_tag.get(), b.d_wq.get(), b.d_tickets.get(), b.d_xref_pm.get(),
-          b.d_track.get(), b.tr_n, b.tr_L, b.tr_width, b.d_trk.get(), b.d_trk_flags.get(), b.d_hp_tag.get(),
+          b.track.d.get(), b.track.n, b.track.L, b.track.width, b.d_trk.get(), b.d_trk_flags.get(), b.d_hp_tag.get(),
           px ? px->d_box.get() : nullptr, px ? px->world : 0, px ? px->rank : 0, px ? px->bound : 0};
 }
 
 // Cancels the armed controller launch waiting on the bank's stream, if any (capi_ctl.hip): the
 // launch exits without touching anything, and work enqueued after it runs once it has.
 void bank_disarm(llampc_bank* b);
+// "This call needs the bank idle": the solver's mutex (or none), then b->mu; the armed launch cancelled;
+// rc, reported through fail(), if an async tick is outstanding; the bank's device current.  An entry
+// with checks of its own between the two locks takes its solver's mutex itself.
+struct BankIdle {
+  std::unique_lock<std::mutex> ls, lk;
+  int rc;
+  DeviceGuard g;
+  explicit BankIdle(llampc_bank* b, std::mutex* solver = nullptr)
+      : ls(solver ? std::unique_lock<std::mutex>(*solver) : std::unique_lock<std::mutex>()), lk(b->mu),
+        rc((bank_disarm(b), b->async_pending) ? fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank") : LLAMPC_OK),
+        g(b->device) {}
+};
 // The bank's own stream on a hardware queue of its own (the caller holds b->mu; nothing armed).
 int bank_dedicate(llampc_bank* b);
 // plan_in_refused of the bank's facts, reported through fail() (capi_plan.hip; the caller holds b->mu
@@ -239,8 +273,13 @@ int check_plan_in(const llampc_bank* b, const llampc_plan_in* in);
 int plan_launch(llampc_bank* b, const llampc_plan_in& in, const llampc::PlanTick& tick);
 inline hipStream_t pick_stream(llampc_bank* b, void* s) { return s ? (hipStream_t)s : b->stream; }
 
-// llampc_nlp_create's checks of a cfg (capi_nlp.hip), llampc_nlp_batch_create's too.
+// llampc_nlp_create's and llampc_nlp_batch_create's: nlp_cfg_invalid reported through fail()
+// (capi_nlp.hip), and nlp_ltraj_flags of the environment (LLAMPC_NLP_RERUN_TRAJ, read here alone).
 int nlp_check_cfg(const llampc_nlp_cfg& k);
+inline llampc::NlpLtraj nlp_create_ltraj(const llampc_nlp_cfg& k) {
+  const char* rt = std::getenv("LLAMPC_NLP_RERUN_TRAJ");
+  return llampc::nlp_ltraj_flags(k, rt && rt[0] == '1');
+}
 
 // Event pair around a GROUP of timing_stride consecutive launches of kernel `k` (0 the plan
 // kernel; 1, 2 reserved): start before the group's first launch, stop after its last, so a
@@ -266,6 +305,16 @@ struct TimedLaunch {
     }
   }
 };
+
+// Deletes a solver bound to a bank (p->b) once the bank's stream has drained.
+template <class S>
+int solver_destroy(S* p) {
+  if (!p) return LLAMPC_OK;
+  DeviceGuard g(p->b->device);
+  if (p->b->stream) (void)hipStreamSynchronize(p->b->stream);
+  delete p;
+  return LLAMPC_OK;
+}
 
 // A handle under construction: a create that fails part-way destroys it (llampc_*_destroy).
 template <class H> using Building = std::unique_ptr<H, int (*)(H*)>;

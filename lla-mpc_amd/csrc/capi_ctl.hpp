@@ -70,9 +70,7 @@ struct llampc_ctl {
   uint64_t dev_ticks = 0;                // the last completed tick's device time (llampc_ctl_device_us)
   std::chrono::steady_clock::time_point arm_t{};
   // the soft track corridor (llampc_ctl_set_track / llampc_ctl_set_corridor; ctl.hpp CtlCorridor)
-  DevBuf<double> d_track;                // cx | cy | tt, [3][tr_n]
-  int32_t tr_n = 0;                      // 0: no track set
-  double tr_L = 0.0, tr_width = 0.0;
+  TrackTables track;
   double cor_w = 0.0, cor_margin = 0.0;  // weight 0: off (the tick launches ctl_kernel)
   bool cor_prev = false;                 // the last tick enqueued was a corridor tick (CtlCorridor.path_ok)
   DevBuf<double> d_cor;                  // the path copies and the read-back copies (capi_host.hpp ctl_cor_layout)
@@ -101,7 +99,7 @@ static inline llampc::CtlView ctl_view(const llampc_ctl& c) {
           c.d_gparams.get(), c.n_global,
           mb != nullptr, mb ? mb->d_box.get() : nullptr, mb ? mb->world : 0, mb ? mb->rank : 0, mb ? mb->bound : 0,
           c.xg_world, c.xg_rank, c.d_xsend.get(), c.d_xgath.get(),
-          c.d_track.get(), c.tr_n, c.tr_L, c.tr_width, c.cor_w, c.cor_margin,
+          c.track.d.get(), c.track.n, c.track.L, c.track.width, c.cor_w, c.cor_margin,
           c.d_cor.get(), c.d_cor_flag.get(), c.d_hp_tag.get(), c.d_cor_cost.get()};
 }
 

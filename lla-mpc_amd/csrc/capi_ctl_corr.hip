@@ -19,17 +19,7 @@ int llampc_ctl_set_track(llampc_ctl* c, const double* centre, const double* thet
   std::lock_guard<std::mutex> lk(b->mu);
   bank_disarm(b);
   DeviceGuard g(b->device);
-  HIP_TRY(hipStreamSynchronize(b->stream));      // no launch reads the tables being replaced
-  c->tr_n = 0;
-  if (int rc = c->d_track.reserve(3 * (size_t)n, 0, "track tables")) return rc;
-  std::vector<double> h(3 * (size_t)n);
-  std::memcpy(h.data(), centre, 2 * (size_t)n * sizeof(double));
-  std::memcpy(h.data() + 2 * (size_t)n, theta, (size_t)n * sizeof(double));
-  HIP_TRY(hipMemcpy(c->d_track.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->tr_n = n;
-  c->tr_L = track_length;
-  c->tr_width = track_width;
-  return LLAMPC_OK;
+  return c->track.upload(b->stream, centre, theta, n, track_length, track_width);
 }
 
 int llampc_ctl_set_corridor(llampc_ctl* c, double weight, double margin) {
@@ -38,7 +28,7 @@ int llampc_ctl_set_corridor(llampc_ctl* c, double weight, double margin) {
   ctl_cancel(c);                         // as every other call: the tick after launches normally
   llampc_bank* b = c->b;
   const llampc_ctl_cfg& k = c->cfg;
-  const CtlCorridorFacts facts{c->pending, c->mb || c->xg_world, c->no_stage, c->tr_n, c->tr_width, b->n, k.C, k.H, k.K, b->rl_n};
+  const CtlCorridorFacts facts{c->pending, c->mb || c->xg_world, c->no_stage, c->track.n, c->track.width, b->n, k.C, k.H, k.K, b->rl_n};
   char why[256];
   if (int rc = ctl_corridor_refused(facts, weight, margin, why, sizeof why)) return fail(rc, "%s", why);
   if (weight > 0) {

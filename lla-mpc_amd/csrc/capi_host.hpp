@@ -327,13 +327,29 @@ inline const char* nlp_batch_corridor_invalid(int32_t B, int32_t H, const double
   return nullptr;
 }
 
+// A path [2][H+1] as the track entries accept it: the first entry that is not finite, or -1; and the
+// single-path entries' message for it (null if valid, else in buf).
+inline int path_nonfinite(const double* path, int32_t H) {
+  for (int i = 0; i < 2 * (H + 1); ++i)
+    if (!std::isfinite(path[i])) return i;
+  return -1;
+}
+inline const char* path_invalid(const double* path, int32_t H, char* buf, size_t nbuf) {
+  const int i = path_nonfinite(path, H);
+  return i < 0 ? nullptr : (std::snprintf(buf, nbuf, "path: entry %d is not finite", i), buf);
+}
 // The paths [B][2][H+1] of a device-built batch: finite.  Null if valid (else in buf, with the problem).
 inline const char* nlp_batch_paths_invalid(int32_t B, int32_t H, const double* path, char* buf, size_t nbuf) {
-  for (int32_t q = 0; q < B; ++q)
-    for (int i = 0; i < 2 * (H + 1); ++i)
-      if (!std::isfinite(path[2 * (size_t)(H + 1) * q + i]))
-        return (std::snprintf(buf, nbuf, "problem %d: path entry %d is not finite", q, i), buf);
+  for (int32_t q = 0; q < B; ++q) {
+    const int i = path_nonfinite(path + 2 * (size_t)(H + 1) * q, H);
+    if (i >= 0) return (std::snprintf(buf, nbuf, "problem %d: path entry %d is not finite", q, i), buf);
+  }
   return nullptr;
+}
+// A corridor margin on a track of this width, as every entry that takes one accepts it: null if valid.
+inline const char* track_margin_refused(double margin, double track_width, char* buf, size_t nbuf) {
+  if (std::isfinite(margin) && track_width / 2 - margin > 0) return nullptr;
+  return (std::snprintf(buf, nbuf, "margin %g leaves no corridor (track width %g)", margin, track_width), buf);
 }
 
 // A problem's max_slack: corridor_max_slack of its returned trajectory; 0 for a problem whose tag
@@ -341,6 +357,116 @@ inline const char* nlp_batch_paths_invalid(int32_t B, int32_t H, const double* p
 inline double nlp_batch_slack(bool arrived, int32_t best_it, const double* hp, const double* traj, int32_t H) {
   return arrived && best_it >= 0 ? corridor_max_slack(hp, traj, H) : 0.0;
 }
+
+// ---- the NLP solve's host path (capi_nlp.hip nlp_solve, capi_nlp_batch.hip nlp_batch_run) --------
+// Both solves are the same six steps: guard, refuse, pack, enqueue, wait, unpack.  The call number
+// (`calls`: the tag sequence host_seq = calls + 1 and the Philox counter word) advances once a solve's
+// launches were enqueued, whatever its wait returned, so that none of its tagged words matches a later
+// round's tag; a call refused before its enqueue leaves it alone.
+//
+// llampc_nlp_create's and llampc_nlp_batch_create's checks of a cfg: null if valid (else in buf).
+inline const char* nlp_cfg_invalid(const llampc_nlp_cfg& k, char* buf, size_t nbuf) {
+  if (k.H < 1 || k.H > LLAMPC_HMAX) return (std::snprintf(buf, nbuf, "H=%d outside [1, %d]", k.H, LLAMPC_HMAX), buf);
+  if (k.samples < 64 || k.samples > 4096 || (k.samples & (k.samples - 1)))
+    return (std::snprintf(buf, nbuf, "samples=%d: a power of two in [64, 4096]", k.samples), buf);
+  if (k.elite < 1 || k.elite > 64 || k.elite > k.samples || k.iters < 1 || k.iters > kNlpMaxIters)
+    return (std::snprintf(buf, nbuf, "elite=%d (1..64, <= samples) iters=%d (1..%d)", k.elite, k.iters, kNlpMaxIters), buf);
+  if (!(k.Ts > 0) || !std::isfinite(k.Ts)) return "Ts must be finite > 0";
+  if (nlp_lds_bytes(k.H, k.samples, k.elite) > kNlpLdsMax) return "H x elite too large for LDS";
+  return nullptr;
+}
+// What a corridor solve refuses of a cfg that passed nlp_cfg_invalid: null if valid.
+inline const char* nlp_corridor_cfg_invalid(const llampc_nlp_cfg& k) {
+  return nlp_corridor_lds_bytes(k.H, k.samples, k.elite) > kNlpLdsMax ? "H x elite too large for LDS with a corridor" : nullptr;
+}
+
+// NlpLaunch.ltraj of a solver's plain and corridor solves (the corridor's LDS holds the half-planes
+// too).  rerun: LLAMPC_NLP_RERUN_TRAJ=1 at create — always the re-run trajectory (tests).
+struct NlpLtraj {
+  bool plain, corridor;
+};
+inline NlpLtraj nlp_ltraj_flags(const llampc_nlp_cfg& k, bool rerun) {
+  return {!rerun && nlp_ltraj_fits(k.H, k.samples, k.elite), !rerun && nlp_corridor_ltraj_fits(k.H, k.samples, k.elite)};
+}
+
+// What a solve's launch takes from its solver beside nlp_launch_cfg: problem 0's buffers, the call
+// number, and which kernel (corridor) and how many rounds the launch is for.
+struct NlpCallView {
+  NlpState* st;  uint64_t* list_tag;  double* cand;  uint64_t* ms_tag;
+  NlpResult* res;  uint64_t* host_tag;   // device aliases of the pinned result and tag
+  uint64_t calls;
+  bool corridor;
+  NlpLtraj ltraj;
+  int32_t rounds;                        // from round 0 on (a launch per round: the caller advances a.it)
+};
+inline void nlp_launch_args(NlpLaunch& a, const NlpCallView& v) {
+  a.st = v.st;
+  a.list_tag = v.list_tag;
+  a.cand = v.cand;
+  a.ms_tag = v.ms_tag;
+  a.res = v.res;
+  a.host_tag = v.host_tag;
+  a.host_seq = v.calls + 1;
+  a.call = v.calls;
+  a.ltraj = v.corridor ? v.ltraj.corridor : v.ltraj.plain;
+  a.it = 0;
+  a.rounds = v.rounds;
+}
+
+// The single solve's inputs as kernel arguments: x0 [6] | xref [2][H+1] | the first mean [H][2] (base,
+// or null = uprev held); the rest of pk is not touched.  nlp_batch_pack's counterpart.
+inline void nlp_inline_pack(NlpInline& pk, int32_t H, const double* x0, const double* xref, const double* uprev,
+                            const double* base) {
+  std::memcpy(pk.v, x0, 6 * sizeof(double));
+  std::memcpy(pk.v + 6, xref, 2 * ((size_t)H + 1) * sizeof(double));
+  double* m0 = pk.v + 6 + 2 * ((size_t)H + 1);
+  for (int i = 0; i < H; ++i)
+    for (int j = 0; j < 2; ++j) m0[2 * i + j] = base ? base[2 * i + j] : uprev[j];
+}
+
+// A result whose tag arrived, into umpc [H][2], fval and xmpc [H+1][6] (either may be null): its status.
+inline int32_t nlp_result_unpack(const NlpResult& r, int32_t H, double* umpc, double* fval, double* xmpc) {
+  std::memcpy(umpc, &r.best_u[0][0], 2 * (size_t)H * sizeof(double));
+  if (fval) *fval = r.best_j;
+  if (xmpc) std::memcpy(xmpc, &r.traj[0][0], 6 * ((size_t)H + 1) * sizeof(double));
+  return r.best_it >= 0 ? LLAMPC_NLP_OK : LLAMPC_NLP_NO_FINITE;
+}
+// A batch's problem: as above if it solved; else umpc zeros and fval +inf, xmpc the trajectory if the
+// tag arrived (no finite objective) and zeros if it did not.
+inline int32_t nlp_batch_unpack(const NlpResult& r, bool arrived, int32_t H, double* umpc, double* fval, double* xmpc) {
+  if (arrived && r.best_it >= 0) return nlp_result_unpack(r, H, umpc, fval, xmpc);
+  std::memset(umpc, 0, 2 * (size_t)H * sizeof(double));
+  *fval = HUGE_VAL;
+  if (arrived) std::memcpy(xmpc, &r.traj[0][0], 6 * ((size_t)H + 1) * sizeof(double));
+  else std::memset(xmpc, 0, 6 * ((size_t)H + 1) * sizeof(double));
+  return arrived ? LLAMPC_NLP_NO_FINITE : LLAMPC_NLP_NO_TAG;
+}
+
+// The device-built half-planes of a track solve, once the stream has drained past their kernel: out of
+// the mapped buffer (`mapped` [H][6]), copied to hp_out (or null), checked, and the slack of traj on them
+// (solved: nlp_batch_slack's rule; slack may be null).  Null, or corridor_invalid's word on them.
+inline const char* nlp_built_corridor(const double* mapped, int32_t H, double weight, double* hp_out, bool solved,
+                                      const double* traj, double* slack) {
+  double built[6 * LLAMPC_HMAX];
+  std::memcpy(built, mapped, 6 * (size_t)H * sizeof(double));
+  if (hp_out) std::memcpy(hp_out, built, 6 * (size_t)H * sizeof(double));
+  if (const char* why = corridor_invalid(built, H, weight)) return why;
+  if (slack) *slack = solved ? corridor_max_slack(built, traj, H) : 0.0;
+  return nullptr;
+}
+
+// What a corridor solve adds to a solve of B problems (the single solver: B = 1), by mode.  given: the
+// caller's half-planes src = hp [B][H][6], checked by the caller; track: the track's along src = path
+// [B][2][H+1], built on the device ahead of the search, margin inside the track's edge (hp_out [B][H][6]
+// or null: what the kernel built).  weight [B], max_slack [B] (the single solver's may be null).
+enum class NlpCorridorMode { none, given, track };
+struct NlpCorridorArgs {
+  NlpCorridorMode mode = NlpCorridorMode::none;
+  const double *src = nullptr, *weight = nullptr;
+  double* max_slack = nullptr;
+  double margin = 0.0;
+  double* hp_out = nullptr;
+};
 
 // The polled completion's wait bound in s_memrealtime ticks (100 MHz): a 2 s floor plus
 // 40 ns per look-ahead rollout step of the launch (a rate floor of 2.5e7 steps/s, ~10^3
@@ -1239,8 +1365,7 @@ inline int ctl_corridor_refused(const CtlCorridorFacts& f, double weight, double
   if (!f.tr_n) LLAMPC_REFUSE(LLAMPC_E_STATE, "no track set: call llampc_ctl_set_track first");
   if (f.sharded) LLAMPC_REFUSE(LLAMPC_E_STATE, "a sharded controller has no corridor ticks");
   if (!(weight >= 0) || !std::isfinite(weight)) LLAMPC_REFUSE(LLAMPC_E_ARG, "weight must be finite and >= 0");
-  if (!std::isfinite(margin) || !(f.tr_width / 2 - margin > 0))
-    LLAMPC_REFUSE(LLAMPC_E_ARG, "margin %g leaves no corridor (track width %g)", margin, f.tr_width);
+  if (track_margin_refused(margin, f.tr_width, buf, nbuf)) return LLAMPC_E_ARG;
   if (weight > 0) {
     const CtlShape V = ctl_shape(f.n, f.C, f.H, f.K, f.rl_n, false, true, f.no_stage, 0, f.tr_n);
     if (V.lds > kCtlLdsMax) LLAMPC_REFUSE(LLAMPC_E_ARG, "a corridor tick needs %zu B of LDS (> 160 KiB)", V.lds);

@@ -30,27 +30,135 @@ struct __attribute__((visibility("hidden"))) llampc_nlp_batch {
   Mapped<uint64_t> in;                   // [max_batch][rec_words] the problems' records
   Mapped<NlpResult> res;                 // [max_batch]
   Mapped<uint64_t> tag;                  // [max_batch][tag_words]: word 0 the problem's tag
-  bool ltraj = false;                    // as llampc_nlp (LLAMPC_NLP_RERUN_TRAJ=1 at create: re-run)
-  bool ltraj_cor = false;                // ltraj of a corridor solve (its LDS holds the half-planes too)
+  NlpLtraj ltraj{};                      // as llampc_nlp
   NlpBatchCorLayout cl{};
   Mapped<double> cor;                    // [max_batch][cor_doubles]: hp | theta | weight per problem
   Mapped<double> path;                   // [max_batch][path_doubles]: the device builder's paths
-  DevBuf<double> d_track;                // llampc_nlp_batch_set_track: cx | cy | tt, [3][tr_n]
-  int32_t tr_n = 0;                      // 0: no track set
-  double tr_L = 0.0, tr_width = 0.0;
+  TrackTables track;                     // llampc_nlp_batch_set_track
   uint64_t calls = 0;                    // one solve number per call, every problem's
   std::mutex mu;
 };
 
-extern "C" {
+namespace {
 
-int llampc_nlp_batch_destroy(llampc_nlp_batch* p) {
-  if (!p) return LLAMPC_OK;
-  DeviceGuard g(p->b->device);
-  if (p->b->stream) (void)hipStreamSynchronize(p->b->stream);
-  delete p;
+// What the device corridor needs before anything is launched (the caller holds p->mu): a track, finite
+// paths and a margin that leaves a corridor (llampc_nlp_solve_track's checks, per problem).
+int batch_track_args(const llampc_nlp_batch* p, int32_t B, const double* path, double margin) {
+  char why[96];
+  if (!p->track.n) return fail(LLAMPC_E_STATE, "no track set: call llampc_nlp_batch_set_track first");
+  if (nlp_batch_paths_invalid(B, p->cfg.H, path, why, sizeof why) || track_margin_refused(margin, p->track.width, why, sizeof why))
+    return fail(LLAMPC_E_ARG, "%s", why);
   return LLAMPC_OK;
 }
+
+// Enqueues track_corridor_batch_kernel on s: the half-planes along the B paths into the problems'
+// parts of the corridor buffer, which start as NaN (nlp_batch_cor_pack) so that a row the kernel did
+// not write fails corridor_invalid afterwards.  weight: [B] or null (the builder alone).
+int enqueue_batch_track_corridor(llampc_nlp_batch* p, int32_t B, const double* path, double margin,
+                                 const double* weight, hipStream_t s) {
+  const int H = p->cfg.H;
+  const NlpBatchCorLayout& c = p->cl;
+  for (int32_t q = 0; q < B; ++q) {
+    std::memcpy(p->path.get() + q * c.path_doubles, path + 2 * (size_t)(H + 1) * q, 2 * (size_t)(H + 1) * sizeof(double));
+    nlp_batch_cor_pack(c, H, p->cor.get() + q * c.cor_doubles, nullptr, weight ? weight[q] : 0.0);
+  }
+  TimedLaunch tl(p->b, 1, s);              // llampc_bank_timing's kernel 1: the corridor kernel alone
+  HIP_TRY(launch_track_corridor_batch(p->track.view(), p->path.dev(), (uint32_t)c.path_doubles, B, H,
+                                      p->track.width / 2 - margin, p->cor.dev(), (uint32_t)c.cor_doubles,
+                                      (uint32_t)c.theta_off, s));
+  p->b->launches++;
+  return LLAMPC_OK;
+}
+
+// One batched solve's inputs and outputs, [B] of llampc_nlp_solve's each, and the corridor's.
+struct NlpBatchArgs {
+  int32_t B;
+  const int64_t* model_idx;
+  const uint64_t* seed;
+  const double *x0, *xref, *uprev, *base;
+  const int32_t* has_hold;
+  double *umpc, *fval, *xmpc;
+  int32_t* status;
+  NlpCorridorArgs cor;
+};
+
+int nlp_batch_run(llampc_nlp_batch* p, const NlpBatchArgs& q) {
+  std::lock_guard<std::mutex> lp(p->mu);
+  llampc_bank* b = p->b;
+  const int32_t B = q.B;
+  if (const char* why = nlp_batch_args_invalid(B, p->max_batch, q.model_idx, b->n, q.x0, q.xref, q.uprev, q.has_hold, q.umpc,
+                                               q.fval, q.xmpc, q.status))
+    return fail(LLAMPC_E_ARG, "NLP batch solve: %s (B=%d, max_batch=%d, n=%lld)", why, B, p->max_batch, (long long)b->n);
+  const llampc_nlp_cfg& k = p->cfg;
+  const NlpCorridorArgs& cr = q.cor;
+  const bool corridor = cr.mode != NlpCorridorMode::none, track = cr.mode == NlpCorridorMode::track;
+  if (corridor) {
+    char why[160];
+    if (!cr.max_slack) return fail(LLAMPC_E_ARG, "NLP batch solve: max_slack is NULL");
+    if (nlp_batch_corridor_invalid(B, k.H, track ? nullptr : cr.src, cr.weight, why, sizeof why))
+      return fail(LLAMPC_E_ARG, "NLP batch corridor: %s", why);
+    if (const char* lds = nlp_corridor_cfg_invalid(k)) return fail(LLAMPC_E_ARG, "%s", lds);
+  }
+  BankIdle idle(b);
+  if (idle.rc) return idle.rc;
+  const NlpBatchLayout& l = p->lay;
+  const NlpBatchCorLayout& c = p->cl;
+  const size_t H = (size_t)k.H;
+  hipStream_t s = b->stream;
+  // all B x nl blocks resident at once: checked at create for max_batch, and B <= max_batch
+  if ((int64_t)B * (k.samples / 64) > b->cus) return fail(LLAMPC_E_ARG, "NLP batch solve: B x samples / 64 exceeds the CUs");
+  if (int rc = track ? batch_track_args(p, B, cr.src, cr.margin) : 0) return rc;
+  for (int32_t i = 0; i < B; ++i) {
+    const int32_t hold = q.has_hold[i] != 0;
+    nlp_batch_pack(l, k.H, p->in.get() + i * l.rec_words, q.x0 + 6 * i, q.xref + 2 * (H + 1) * i, q.uprev + 2 * i,
+                   q.base && hold ? q.base + 2 * H * i : nullptr, q.seed ? q.seed[i] : k.seed, q.model_idx[i], hold);
+    if (cr.mode == NlpCorridorMode::given)
+      nlp_batch_cor_pack(c, k.H, p->cor.get() + i * c.cor_doubles, cr.src + 6 * H * i, cr.weight[i]);
+  }
+  if (int rc = track ? enqueue_batch_track_corridor(p, B, cr.src, cr.margin, cr.weight, s) : 0) return rc;
+  NlpLaunch a{};
+  nlp_launch_cfg(a, k, b->veh, b->d_params.get(), b->n);
+  // always every round in one launch
+  nlp_launch_args(a, {p->d_st.get(), p->d_list.get(), p->d_cand.get(), p->d_ms_tag.get(), p->res.dev(), p->tag.dev(),
+                      p->calls, corridor, p->ltraj, k.iters});
+  const NlpBatch bt = nlp_batch_arg(l, p->in.dev(), k.samples);
+  {
+    TimedLaunch tl(b, 0, s);             // llampc_bank_timing on the bank: per batched solve
+    HIP_TRY(corridor ? launch_nlp_batch_corridor(a, nlp_batch_cor_arg(bt, c, p->cor.dev()), B, s)
+                     : launch_nlp_batch(a, bt, B, s));
+  }
+  const uint64_t want = p->calls + 1;
+  const std::unique_ptr<bool[]> arrived(new bool[B]());
+  const int rc = spin_for_tags(p->tag.get(), l.tag_words, B, want, arrived.get(), [&]() -> int {
+    HIP_TRY(hipStreamSynchronize(s));
+    return LLAMPC_OK;
+  });
+  p->calls++;                            // capi_host.hpp: whatever the wait returned
+  if (rc) return rc;
+  b->launches++;
+  const NlpResult* r = const_cast<const NlpResult*>(p->res.get());
+  for (int32_t i = 0; i < B; ++i)
+    q.status[i] = nlp_batch_unpack(r[i], arrived[i], k.H, q.umpc + 2 * H * i, q.fval + i, q.xmpc + 6 * (H + 1) * i);
+  // a device-built corridor: the stream has drained past its kernel if any problem's tag arrived; if
+  // none did, spin_for_tags' timeout handler synchronised it
+  for (int32_t i = 0; corridor && i < B; ++i) {
+    const double* traj = &r[i].traj[0][0];
+    if (!track) {
+      cr.max_slack[i] = nlp_batch_slack(arrived[i], r[i].best_it, cr.src + 6 * H * i, traj, k.H);
+    } else if (const char* why = nlp_built_corridor(p->cor.get() + i * c.cor_doubles, k.H, cr.weight[i],
+                                                    cr.hp_out ? cr.hp_out + 6 * H * i : nullptr,
+                                                    q.status[i] == LLAMPC_NLP_OK, traj, cr.max_slack + i)) {
+      return fail(LLAMPC_E_DEVICE, "the device-built corridor of problem %d: %s", i, why);
+    }
+  }
+  return LLAMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int llampc_nlp_batch_destroy(llampc_nlp_batch* p) { return solver_destroy(p); }
 
 int llampc_nlp_batch_create(llampc_bank* b, const llampc_nlp_cfg* cfg, int32_t max_batch, llampc_nlp_batch** out) {
   if (!out) return fail(LLAMPC_E_ARG, "out is NULL");
@@ -80,9 +188,7 @@ int llampc_nlp_batch_create(llampc_bank* b, const llampc_nlp_cfg* cfg, int32_t m
   if ((rc = p->cor.alloc(mb * p->cl.cor_doubles, "NLP batch corridors")) ||
       (rc = p->path.alloc(mb * p->cl.path_doubles, "NLP batch corridor paths")))
     return rc;
-  const char* rt = std::getenv("LLAMPC_NLP_RERUN_TRAJ");
-  p->ltraj = nlp_ltraj_fits(k.H, k.samples, k.elite) && !(rt && rt[0] == '1');
-  p->ltraj_cor = nlp_corridor_ltraj_fits(k.H, k.samples, k.elite) && !(rt && rt[0] == '1');
+  p->ltraj = nlp_create_ltraj(k);
   if (hipDeviceSynchronize() != hipSuccess) return fail(LLAMPC_E_HIP, "NLP batch solver upload failed");
   *out = p.release();
   return LLAMPC_OK;
@@ -95,161 +201,11 @@ int llampc_nlp_batch_info(const llampc_nlp_batch* p, int32_t* max_batch, int32_t
   return LLAMPC_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// What a corridor solve adds to the batched solve: the caller's half-planes hp [B][H][6] (checked by
-// the caller), or the track's along path [B][2][H+1] built on the device ahead of the search
-// (hp null; hp_out [B][H][6] or null: what the kernel built), the weights [B] and max_slack [B].
-struct BatchCorridorArgs {
-  const double* hp = nullptr;
-  const double* path = nullptr;
-  double margin = 0.0;
-  const double* weight = nullptr;
-  double* max_slack = nullptr;
-  double* hp_out = nullptr;
-};
-
-// What the device corridor needs before anything is launched (the caller holds p->mu): a track, finite
-// paths and a margin that leaves a corridor (llampc_nlp_solve_track's checks, per problem).
-int batch_track_args(const llampc_nlp_batch* p, int32_t B, const double* path, double margin) {
-  if (!p->tr_n) return fail(LLAMPC_E_STATE, "no track set: call llampc_nlp_batch_set_track first");
-  char why[96];
-  if (nlp_batch_paths_invalid(B, p->cfg.H, path, why, sizeof why)) return fail(LLAMPC_E_ARG, "%s", why);
-  if (!std::isfinite(margin) || !(p->tr_width / 2 - margin > 0))
-    return fail(LLAMPC_E_ARG, "margin %g leaves no corridor (track width %g)", margin, p->tr_width);
-  return LLAMPC_OK;
-}
-
-// Enqueues track_corridor_batch_kernel on s: the half-planes along the B paths into the problems'
-// parts of the corridor buffer, which start as NaN (nlp_batch_cor_pack) so that a row the kernel did
-// not write fails corridor_invalid afterwards.  weight: [B] or null (the builder alone).
-int enqueue_batch_track_corridor(llampc_nlp_batch* p, int32_t B, const double* path, double margin,
-                                 const double* weight, hipStream_t s) {
-  const int H = p->cfg.H;
-  const NlpBatchCorLayout& c = p->cl;
-  for (int32_t q = 0; q < B; ++q) {
-    std::memcpy(p->path.get() + q * c.path_doubles, path + 2 * (size_t)(H + 1) * q, 2 * (size_t)(H + 1) * sizeof(double));
-    nlp_batch_cor_pack(c, H, p->cor.get() + q * c.cor_doubles, nullptr, weight ? weight[q] : 0.0);
-  }
-  const size_t n = (size_t)p->tr_n;
-  const double* d = p->d_track.get();
-  const TrackK t{d, d + n, d + 2 * n, p->tr_n, 0, p->tr_L};
-  TimedLaunch tl(p->b, 1, s);              // llampc_bank_timing's kernel 1: the corridor kernel alone
-  HIP_TRY(launch_track_corridor_batch(t, p->path.dev(), (uint32_t)c.path_doubles, B, H, p->tr_width / 2 - margin,
-                                      p->cor.dev(), (uint32_t)c.cor_doubles, (uint32_t)c.theta_off, s));
-  p->b->launches++;
-  return LLAMPC_OK;
-}
-
-// One batched solve: the unconstrained search (cr null: llampc_nlp_batch_solve) or the corridor's.
-int nlp_batch_run(llampc_nlp_batch* p, int32_t B, const int64_t* model_idx, const uint64_t* seed, const double* x0,
-                  const double* xref, const double* uprev, const double* base, const int32_t* has_hold, double* umpc,
-                  double* fval, double* xmpc, int32_t* status, const BatchCorridorArgs* cr) {
-  std::lock_guard<std::mutex> lp(p->mu);
-  llampc_bank* b = p->b;
-  if (const char* why = nlp_batch_args_invalid(B, p->max_batch, model_idx, b->n, x0, xref, uprev, has_hold, umpc, fval,
-                                               xmpc, status))
-    return fail(LLAMPC_E_ARG, "NLP batch solve: %s (B=%d, max_batch=%d, n=%lld)", why, B, p->max_batch, (long long)b->n);
-  const llampc_nlp_cfg& k = p->cfg;
-  if (cr) {
-    char why[160];
-    if (!cr->max_slack) return fail(LLAMPC_E_ARG, "NLP batch solve: max_slack is NULL");
-    if (nlp_batch_corridor_invalid(B, k.H, cr->hp, cr->weight, why, sizeof why))
-      return fail(LLAMPC_E_ARG, "NLP batch corridor: %s", why);
-    if (nlp_corridor_lds_bytes(k.H, k.samples, k.elite) > 160 * 1024)
-      return fail(LLAMPC_E_ARG, "H x elite too large for LDS with a corridor");
-  }
-  std::lock_guard<std::mutex> lk(b->mu);
-  bank_disarm(b);
-  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
-  DeviceGuard g(b->device);
-  const NlpBatchLayout& l = p->lay;
-  const NlpBatchCorLayout& c = p->cl;
-  const size_t H = (size_t)k.H;
-  hipStream_t s = b->stream;
-  // all B x nl blocks resident at once: checked at create for max_batch, and B <= max_batch
-  if ((int64_t)B * (k.samples / 64) > b->cus) return fail(LLAMPC_E_ARG, "NLP batch solve: B x samples / 64 exceeds the CUs");
-  if (cr && cr->path)
-    if (int rc = batch_track_args(p, B, cr->path, cr->margin)) return rc;
-  for (int32_t q = 0; q < B; ++q) {
-    const int32_t hold = has_hold[q] != 0;
-    nlp_batch_pack(l, k.H, p->in.get() + q * l.rec_words, x0 + 6 * q, xref + 2 * (H + 1) * q, uprev + 2 * q,
-                   base && hold ? base + 2 * H * q : nullptr, seed ? seed[q] : k.seed, model_idx[q], hold);
-    if (cr && cr->hp) nlp_batch_cor_pack(c, k.H, p->cor.get() + q * c.cor_doubles, cr->hp + 6 * H * q, cr->weight[q]);
-  }
-  if (cr && cr->path)
-    if (int rc = enqueue_batch_track_corridor(p, B, cr->path, cr->margin, cr->weight, s)) return rc;
-  NlpLaunch a{};
-  nlp_launch_cfg(a, k, b->veh, b->d_params.get(), b->n);
-  a.st = p->d_st.get();
-  a.list_tag = p->d_list.get();
-  a.cand = p->d_cand.get();
-  a.ms_tag = p->d_ms_tag.get();
-  a.res = p->res.dev();
-  a.host_tag = p->tag.dev();
-  a.host_seq = p->calls + 1;
-  a.call = p->calls;
-  a.ltraj = cr ? p->ltraj_cor : p->ltraj;
-  a.it = 0;                             // always every round in one launch
-  a.rounds = k.iters;
-  const NlpBatch bt = nlp_batch_arg(l, p->in.dev(), k.samples);
-  {
-    TimedLaunch tl(b, 0, s);             // llampc_bank_timing on the bank: per batched solve
-    if (cr) {
-      HIP_TRY(launch_nlp_batch_corridor(a, nlp_batch_cor_arg(bt, c, p->cor.dev()), B, s));
-    } else {
-      HIP_TRY(launch_nlp_batch(a, bt, B, s));
-    }
-  }
-  const uint64_t want = p->calls + 1;
-  const std::unique_ptr<bool[]> arrived(new bool[B]());
-  const int rc = spin_for_tags(p->tag.get(), l.tag_words, B, want, arrived.get(), [&]() -> int {
-    HIP_TRY(hipStreamSynchronize(s));
-    return LLAMPC_OK;
-  });
-  // a new call number whatever happened: none of this solve's tagged words matches a later round's
-  p->calls++;
-  if (rc) return rc;
-  b->launches++;
-  const NlpResult* r = const_cast<const NlpResult*>(p->res.get());
-  for (int32_t q = 0; q < B; ++q) {
-    const bool ok = arrived[q] && r[q].best_it >= 0;
-    status[q] = !arrived[q] ? LLAMPC_NLP_NO_TAG : (ok ? LLAMPC_NLP_OK : LLAMPC_NLP_NO_FINITE);
-    for (size_t i = 0; i < 2 * H; ++i) umpc[2 * H * q + i] = ok ? (&r[q].best_u[0][0])[i] : 0.0;
-    fval[q] = ok ? r[q].best_j : HUGE_VAL;
-    if (arrived[q]) std::memcpy(xmpc + 6 * (H + 1) * q, &r[q].traj[0][0], 6 * (H + 1) * sizeof(double));
-    else std::memset(xmpc + 6 * (H + 1) * q, 0, 6 * (H + 1) * sizeof(double));
-  }
-  if (!cr) return LLAMPC_OK;
-  if (cr->path) {
-    // the stream has drained past the corridor kernel if any problem's tag arrived; if none did,
-    // spin_for_tags' timeout handler synchronised it
-    for (int32_t q = 0; q < B; ++q) {
-      double built[6 * LLAMPC_HMAX];
-      std::memcpy(built, p->cor.get() + q * c.cor_doubles, 6 * H * sizeof(double));
-      if (cr->hp_out) std::memcpy(cr->hp_out + 6 * H * q, built, 6 * H * sizeof(double));
-      if (const char* why = corridor_invalid(built, k.H, cr->weight[q]))
-        return fail(LLAMPC_E_DEVICE, "the device-built corridor of problem %d: %s", q, why);
-      cr->max_slack[q] = nlp_batch_slack(arrived[q], r[q].best_it, built, &r[q].traj[0][0], k.H);
-    }
-  } else {
-    for (int32_t q = 0; q < B; ++q)
-      cr->max_slack[q] = nlp_batch_slack(arrived[q], r[q].best_it, cr->hp + 6 * H * q, &r[q].traj[0][0], k.H);
-  }
-  return LLAMPC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int llampc_nlp_batch_solve(llampc_nlp_batch* p, int32_t B, const int64_t* model_idx, const uint64_t* seed,
                            const double* x0, const double* xref, const double* uprev, const double* base,
                            const int32_t* has_hold, double* umpc, double* fval, double* xmpc, int32_t* status) {
   if (!p) return fail(LLAMPC_E_ARG, "NULL argument");
-  return nlp_batch_run(p, B, model_idx, seed, x0, xref, uprev, base, has_hold, umpc, fval, xmpc, status, nullptr);
+  return nlp_batch_run(p, {B, model_idx, seed, x0, xref, uprev, base, has_hold, umpc, fval, xmpc, status, {}});
 }
 
 int llampc_nlp_batch_solve_corridor(llampc_nlp_batch* p, int32_t B, const int64_t* model_idx, const uint64_t* seed,
@@ -258,11 +214,8 @@ int llampc_nlp_batch_solve_corridor(llampc_nlp_batch* p, int32_t B, const int64_
                                     double* fval, double* xmpc, int32_t* status, double* max_slack) {
   if (!p) return fail(LLAMPC_E_ARG, "NULL argument");
   if (!hp) return fail(LLAMPC_E_ARG, "hp is NULL (llampc_nlp_batch_solve is the unconstrained solve)");
-  BatchCorridorArgs cr;
-  cr.hp = hp;
-  cr.weight = weight;
-  cr.max_slack = max_slack;
-  return nlp_batch_run(p, B, model_idx, seed, x0, xref, uprev, base, has_hold, umpc, fval, xmpc, status, &cr);
+  const NlpCorridorArgs cr{NlpCorridorMode::given, hp, weight, max_slack};
+  return nlp_batch_run(p, {B, model_idx, seed, x0, xref, uprev, base, has_hold, umpc, fval, xmpc, status, cr});
 }
 
 int llampc_nlp_batch_set_track(llampc_nlp_batch* p, const double* centre, const double* theta, int32_t n,
@@ -270,23 +223,9 @@ int llampc_nlp_batch_set_track(llampc_nlp_batch* p, const double* centre, const 
   if (!p || !centre || !theta) return fail(LLAMPC_E_ARG, "NULL argument");
   char why[128];
   if (track_tables_invalid(centre, theta, n, track_length, track_width, why, sizeof why)) return fail(LLAMPC_E_ARG, "%s", why);
-  std::lock_guard<std::mutex> lp(p->mu);
-  llampc_bank* b = p->b;
-  std::lock_guard<std::mutex> lk(b->mu);
-  bank_disarm(b);
-  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
-  DeviceGuard g(b->device);
-  HIP_TRY(hipStreamSynchronize(b->stream));      // no launch reads the tables being replaced
-  p->tr_n = 0;
-  if (int rc = p->d_track.reserve(3 * (size_t)n, 0, "track tables")) return rc;
-  std::vector<double> h(3 * (size_t)n);
-  std::memcpy(h.data(), centre, 2 * (size_t)n * sizeof(double));
-  std::memcpy(h.data() + 2 * (size_t)n, theta, (size_t)n * sizeof(double));
-  HIP_TRY(hipMemcpy(p->d_track.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  p->tr_n = n;
-  p->tr_L = track_length;
-  p->tr_width = track_width;
-  return LLAMPC_OK;
+  BankIdle idle(p->b, &p->mu);
+  if (idle.rc) return idle.rc;
+  return p->track.upload(p->b->stream, centre, theta, n, track_length, track_width);
 }
 
 int llampc_nlp_batch_solve_track(llampc_nlp_batch* p, int32_t B, const int64_t* model_idx, const uint64_t* seed,
@@ -296,13 +235,8 @@ int llampc_nlp_batch_solve_track(llampc_nlp_batch* p, int32_t B, const int64_t* 
                                  double* hp_out) {
   if (!p) return fail(LLAMPC_E_ARG, "NULL argument");
   if (!path) return fail(LLAMPC_E_ARG, "path is NULL");
-  BatchCorridorArgs cr;
-  cr.path = path;
-  cr.margin = margin;
-  cr.weight = weight;
-  cr.max_slack = max_slack;
-  cr.hp_out = hp_out;
-  return nlp_batch_run(p, B, model_idx, seed, x0, xref, uprev, base, has_hold, umpc, fval, xmpc, status, &cr);
+  const NlpCorridorArgs cr{NlpCorridorMode::track, path, weight, max_slack, margin, hp_out};
+  return nlp_batch_run(p, {B, model_idx, seed, x0, xref, uprev, base, has_hold, umpc, fval, xmpc, status, cr});
 }
 
 int llampc_nlp_batch_track_corridor(llampc_nlp_batch* p, int32_t B, const double* path, double margin, double* hp,
@@ -310,21 +244,18 @@ int llampc_nlp_batch_track_corridor(llampc_nlp_batch* p, int32_t B, const double
   if (!p || !path || !hp) return fail(LLAMPC_E_ARG, "NULL argument");
   std::lock_guard<std::mutex> lp(p->mu);
   if (B < 1 || B > p->max_batch) return fail(LLAMPC_E_ARG, "B=%d outside [1, max_batch=%d]", B, p->max_batch);
-  llampc_bank* b = p->b;
-  std::lock_guard<std::mutex> lk(b->mu);
-  bank_disarm(b);
-  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
-  DeviceGuard g(b->device);
+  BankIdle idle(p->b);
+  if (idle.rc) return idle.rc;
   const size_t H = (size_t)p->cfg.H;
   const NlpBatchCorLayout& c = p->cl;
+  hipStream_t s = p->b->stream;
   if (int rc = batch_track_args(p, B, path, margin)) return rc;
-  if (int rc = enqueue_batch_track_corridor(p, B, path, margin, nullptr, b->stream)) return rc;
-  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (int rc = enqueue_batch_track_corridor(p, B, path, margin, nullptr, s)) return rc;
+  HIP_TRY(hipStreamSynchronize(s));
   for (int32_t q = 0; q < B; ++q) {
     const double* part = p->cor.get() + q * c.cor_doubles;
-    std::memcpy(hp + 6 * H * q, part, 6 * H * sizeof(double));
     if (theta) std::memcpy(theta + H * q, part + c.theta_off, H * sizeof(double));
-    if (const char* why = corridor_invalid(hp + 6 * H * q, (int32_t)H, 0.0))
+    if (const char* why = nlp_built_corridor(part, (int32_t)H, 0.0, hp + 6 * H * q, false, nullptr, nullptr))
       return fail(LLAMPC_E_DEVICE, "the device-built corridor of problem %d: %s", q, why);
   }
   return LLAMPC_OK;

@@ -25,7 +25,7 @@ int plan_launch(llampc_bank* b, const llampc_plan_in& in, const PlanTick& t) {
 namespace {
 
 PlanBankFacts bank_facts(const llampc_bank* b) {
-  return {b->n, static_cast<bool>(b->d_rl), b->tr_n, b->tr_width, b->async_pending};
+  return {b->n, static_cast<bool>(b->d_rl), b->track.n, b->track.width, b->async_pending};
 }
 
 // plan_entry_refused of the bank (the caller holds b->mu), reported through fail().
@@ -371,41 +371,27 @@ int llampc_bank_set_track(llampc_bank* b, const double* centre, const double* th
   if (!b || !centre || !theta) return fail(LLAMPC_E_ARG, "NULL argument");
   char why[128];
   if (track_tables_invalid(centre, theta, n, track_length, track_width, why, sizeof why)) return fail(LLAMPC_E_ARG, "%s", why);
-  std::lock_guard<std::mutex> lk(b->mu);
-  bank_disarm(b);
-  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
-  DeviceGuard g(b->device);
-  HIP_TRY(hipStreamSynchronize(b->stream));      // no launch reads the tables being replaced
-  b->tr_n = 0;
+  BankIdle idle(b);
+  if (idle.rc) return idle.rc;
   b->trk_path = track_path_next(b->trk_path, kPathClear);
   b->trk_last_H = 0;
-  int rc;
-  if ((rc = track_state(b)) || (rc = b->d_track.reserve(3 * (size_t)n, 0, "track tables"))) return rc;
-  std::vector<double> h(3 * (size_t)n);
-  std::memcpy(h.data(), centre, 2 * (size_t)n * sizeof(double));
-  std::memcpy(h.data() + 2 * (size_t)n, theta, (size_t)n * sizeof(double));
-  HIP_TRY(hipMemcpy(b->d_track.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  b->tr_n = n;
-  b->tr_L = track_length;
-  b->tr_width = track_width;
-  return LLAMPC_OK;
+  if (int rc = track_state(b)) return rc;
+  return b->track.upload(b->stream, centre, theta, n, track_length, track_width);
 }
 
 int llampc_bank_set_path(llampc_bank* b, const double* path, int32_t H) {
   if (!b) return fail(LLAMPC_E_ARG, "bank is NULL");
   if (path) {
     if (H < 1 || H > LLAMPC_HMAX) return fail(LLAMPC_E_ARG, "H=%d outside [1, %d]", H, LLAMPC_HMAX);
-    for (int i = 0; i < 2 * (H + 1); ++i)
-      if (!std::isfinite(path[i])) return fail(LLAMPC_E_ARG, "path: entry %d is not finite", i);
+    char why[64];
+    if (path_invalid(path, H, why, sizeof why)) return fail(LLAMPC_E_ARG, "%s", why);
   }
-  std::lock_guard<std::mutex> lk(b->mu);
-  bank_disarm(b);
-  if (b->async_pending) return fail(LLAMPC_E_STATE, "an async tick is outstanding on the bank");
+  BankIdle idle(b);
+  if (idle.rc) return idle.rc;
   if (!path) {
     b->trk_path = track_path_next(b->trk_path, kPathClear);
     return LLAMPC_OK;
   }
-  DeviceGuard g(b->device);
   HIP_TRY(hipStreamSynchronize(b->stream));      // no launch reads or writes the copy being seeded
   if (int rc = track_state(b)) return rc;
   constexpr PlanTrackLayout L = plan_track_layout();

@@ -74,7 +74,7 @@ size_t nlp_lds_bytes(int H, int samples, int elite, bool ltraj) {
   return nlp_traj_off(H, samples / 64, elite) + (ltraj ? 48 * 64 * (size_t)H : 0);
 }
 bool nlp_ltraj_fits(int H, int samples, int elite) {
-  return H <= kNlpStageH && nlp_lds_bytes(H, samples, elite, true) <= 160 * 1024;
+  return H <= kNlpStageH && nlp_lds_bytes(H, samples, elite, true) <= kNlpLdsMax;
 }
 
 hipError_t launch_nlp(const NlpLaunch& a, const NlpInline& pk, hipStream_t s) {
@@ -96,7 +96,7 @@ size_t nlp_corridor_lds_bytes(int H, int samples, int elite, bool ltraj) {
   return nlp_lds_bytes(H, samples, elite, ltraj) + 48 * (size_t)H;
 }
 bool nlp_corridor_ltraj_fits(int H, int samples, int elite) {
-  return H <= kNlpStageH && nlp_corridor_lds_bytes(H, samples, elite, true) <= 160 * 1024;
+  return H <= kNlpStageH && nlp_corridor_lds_bytes(H, samples, elite, true) <= kNlpLdsMax;
 }
 
 hipError_t launch_nlp_corridor(const NlpLaunch& a, const NlpInline& pk, const NlpCorridor& cor, hipStream_t s) {

@@ -87,6 +87,7 @@ __host__ __device__ __forceinline__ int nlp_list_len(int elite) {
   while (l < elite) l <<= 1;
   return l;
 }
+constexpr size_t kNlpLdsMax = 160 * 1024;   // a launch's LDS: the CU's
 size_t nlp_lds_bytes(int H, int samples, int elite, bool ltraj = false);
 bool nlp_ltraj_fits(int H, int samples, int elite);
 hipError_t launch_nlp(const NlpLaunch& a, const NlpInline& pk, hipStream_t s);
