@@ -33,6 +33,10 @@
  *                                  117-154), Dynamic._diffequation_batch (:98-115)
  *  llampc_ctl_*                    the control loop body rt.py:278-366 on the device
  *                                  (ConstantSpeed, selection, look-ahead, mu-hat, state)
+ *  llampc_ctl_step / _solver_*     (new) that body with the selected model's NMPC solve
+ *                                  (rt.py:303-305) chained behind the tick on the device and its
+ *                                  first input committed as the applied one
+ *  llampc_ctl_set_applied          (new) tells the controller the input that was really applied
  *  llampc_integrate_batch          Model._integrate_batch (model.py:32-40, RK4),
  *                                  Model._integrate/odeintRK6 (model.py:18-30,
  *                                  llampc/utils/rk6.py:13-28) and the NLP Euler form
@@ -499,8 +503,19 @@ int llampc_ctl_device_us(llampc_ctl* ctl, double* us);
  * projidx (no lap wrap) and vr.  Blocking; leaves the controller state alone. */
 int llampc_ctl_reference(llampc_ctl* ctl, const double* x0, double v0, int32_t H, int32_t projidx, double curr_mu,
                          double scale, double* xref, int32_t* projidx_out, double* vr);
-/* The last tick's reference xref [2][H+1] and candidates U [C][H][2] (cfg.debug_inputs = 1). */
+/* The last tick's reference xref [2][H+1] and candidates U [C][H][2] (cfg.debug_inputs = 1).  A
+ * fused-step solver (llampc_ctl_solver_create) needs the tick's reference in device memory and
+ * switches the same copy on while it is attached: every tick then also stores its candidates
+ * (16 C H bytes, by one block), and this call answers on a controller created without
+ * debug_inputs too; both end when the solver is destroyed. */
 int llampc_ctl_inputs(llampc_ctl* ctl, double* xref, double* U);
+/* The input really applied after the last tick, when it is not the tick's own u_seq[0] (an NMPC
+ * solve's, a safety override): u0 [2] -> CtlState.u_prev; useq [H][2] or NULL (keep the chosen
+ * sequence, its row 0 replaced by u0) -> CtlState.useq, the next candidates' base.  The next tick's
+ * look-back transition, du_0 and candidate base use the new values; the past record's u_seq stays as
+ * it was.  Needs a completed tick and none outstanding (LLAMPC_E_STATE).  Values must be finite
+ * (LLAMPC_E_ARG).  Takes the bank idle like every other call (cancels an armed launch).  Blocking. */
+int llampc_ctl_set_applied(llampc_ctl* ctl, const double* u0, const double* useq);
 /* ---- the soft track corridor inside the controller tick ----
  * The reference's constraints.py (Boundary(): the track's boundary lines linearised per step, with
  * slack variables in the NLP of nmpc.py:161-203) as a soft term of the candidate search: every
@@ -737,6 +752,53 @@ int llampc_nlp_batch_solve_track(llampc_nlp_batch* nb, int32_t B, const int64_t*
                                  const double* weight /* [B] */, double* umpc, double* fval, double* xmpc,
                                  int32_t* status, double* max_slack /* [B] */, double* hp_out /* [B][H][6] or NULL */);
 int llampc_nlp_batch_destroy(llampc_nlp_batch* nb);
+
+/* ---- the fused control step: the tick and the selected model's NMPC solve, one chain ------ */
+/* The reference's control step (rt.py:269-366): the look-back selects a model, THAT model's NMPC is
+ * solved (nlp_bank[current_model_idx].solve, rt.py:303-305; nlp_initial while the window fills), the
+ * solve's first input is applied, and the next look-back scores the bank on the transition under the
+ * input that was applied.  llampc_ctl_step enqueues all of it on the bank's stream with no host
+ * synchronisation in between and ONE pair of host waits at the end:
+ *   0. snapshot  CtlState.u_prev (zeros before the first tick) -> the solve's du_0 reference
+ *   1. the tick  exactly llampc_ctl_tick_async's launch (same prepare / commit, same kernel); with a
+ *                solver attached it also leaves its reference xref [2][H+1] in device memory
+ *   2. build     one block writes the solve's problem in device memory: x0 = x_t, the tick's xref, the
+ *                first mean = the tick's chosen sequence (not shifted), uprev = the snapshot, has_hold
+ *                = 1; and the model: cfg.nominal of the controller while the tick was warm, else the
+ *                bank column the tick selected
+ *   3. the solve llampc_nlp_batch_solve's kernel, B = 1, unmodified (its result in device memory)
+ *   4. commit    one block: a solve with a finite objective becomes the applied sequence
+ *                (CtlState.u_prev <- umpc[0], CtlState.useq <- umpc; committed = 1); otherwise the
+ *                state stays as the tick left it and the tick's candidate is the applied input.  Then
+ *                the result into the pinned llampc_ctl_solve_out and its tag.
+ * The host waits for the tick's tag (llampc_ctl_wait's path), then the commit's.  The solve's Philox
+ * call word is the number of steps this solver has run (plain ticks in between do not count); it
+ * advances whatever the waits returned.  llampc_bank_timing brackets the whole chain as one launch
+ * group; llampc_bank_launches counts the tick and the solve (2 per step), each once it is enqueued.
+ *
+ * cfg is llampc_nlp_create's, with H and Ts equal to the controller's (LLAMPC_E_ARG), samples / 64 <=
+ * 64 and <= the device's CUs (every round in one launch).  The solver borrows the controller and its
+ * bank: destroy the solver first.  LLAMPC_E_STATE, with nothing launched and the launch counter
+ * unchanged: create on a controller with prelaunch on, with an exchange or a gather transport, with a
+ * corridor weight > 0, with a tick outstanding or with a solver already; and, while a solver is
+ * attached, llampc_ctl_set_prelaunch(1), llampc_ctl_set_corridor(weight > 0), llampc_ctl_set_exchange
+ * and llampc_ctl_set_gather.  A plain llampc_ctl_tick stays allowed: its candidate is then the applied
+ * input.  Not part of this interface: armed, sharded or corridor fused steps (refused as above), the
+ * top-K's side problems, and an asynchronous step_begin / step_end pair. */
+typedef struct llampc_ctl_solver llampc_ctl_solver;
+typedef struct llampc_ctl_solve_out {
+  double umpc[LLAMPC_HMAX][2];     /* [H][2]; zeros unless status == LLAMPC_NLP_OK               */
+  double xmpc[LLAMPC_HMAX + 1][6]; /* [H+1][6] the NLP's Euler trajectory of umpc                */
+  double fval;                     /* +inf unless status == LLAMPC_NLP_OK                        */
+  double uprev[2];                 /* du_0's reference: the state's u_prev as the tick read it   */
+  int64_t model;                   /* global index solved with; -1: the nominal model (warm)     */
+  int32_t status;                  /* LLAMPC_NLP_OK / _NO_FINITE / _NO_TAG                       */
+  int32_t committed;               /* 1: umpc is now the controller's applied sequence           */
+} llampc_ctl_solve_out;
+int llampc_ctl_solver_create(llampc_ctl* ctl, const llampc_nlp_cfg* cfg, llampc_ctl_solver** out);
+/* x_t [6] -> the tick's record and the solve's.  Blocking. */
+int llampc_ctl_step(llampc_ctl_solver* s, const double* x_t, llampc_ctl_out* out, llampc_ctl_solve_out* sol);
+int llampc_ctl_solver_destroy(llampc_ctl_solver* s);
 
 /* ---- raw batched dynamics (Dynamic API parity) ---------------------------------- */
 /* x [n][6], u [n][2]; params [6][P] with P == 1 (one model broadcast) or P == n.

@@ -102,6 +102,18 @@ static void ctl_commit(llampc_ctl* c, const CtlPrep& P) {
   c->b->launches++;
 }
 
+// A launched tick as the fused step enqueues it (capi_ctl.hpp): llampc_ctl_tick_async's refresh and
+// prepare, then `before` (its warm flag; what the caller enqueues ahead of the tick), the tick's one
+// launch and its commit.  A refusal of the prepare, or `before` failing, leaves nothing of the tick.
+int ctl_tick_launched(llampc_ctl* c, const double* x_t, int (*before)(void* arg, int32_t warm), void* arg) {
+  CtlPrep P;
+  int rc;
+  if ((rc = ctl_refresh(c, true)) || (rc = ctl_prepare(c, x_t, P)) || (rc = before(arg, P.L.warm))) return rc;
+  HIP_TRY(ctl_launch(P, c->b->stream));
+  ctl_commit(c, P);
+  return LLAMPC_OK;
+}
+
 // Enqueues tick c->t's launch armed (llampc_ctl_set_prelaunch): it runs behind the tick in
 // flight and waits for the doorbell.  The caller holds c->mu, c->b->mu and, with a peer
 // exchange, c->mb->mu.  With the peer exchange the armed launch takes the mailbox's next tick
@@ -314,6 +326,7 @@ int llampc_ctl_device_us(llampc_ctl* c, double* us) {
 int llampc_ctl_set_prelaunch(llampc_ctl* c, int32_t on) {
   if (!c) return fail(LLAMPC_E_ARG, "controller is NULL");
   std::lock_guard<std::mutex> lc(c->mu);
+  if (const char* why = ctl_solver_blocks(c->solver_attached, CtlSetter::prelaunch, on != 0)) return fail(LLAMPC_E_STATE, "%s", why);
   if (on && c->xg_world) return fail(LLAMPC_E_STATE, "prelaunch is not available with a gather transport");
   llampc_bank* b = c->b;
   std::lock_guard<std::mutex> lk(b->mu);
@@ -394,6 +407,27 @@ int llampc_ctl_inputs(llampc_ctl* c, double* xref, double* U) {
   const size_t nx = 2 * (size_t)(c->cfg.H + 1), nu = 2 * (size_t)c->cfg.C * c->cfg.H;
   HIP_TRY(hipMemcpy(xref, c->d_dbg.get(), nx * sizeof(double), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(U, c->d_dbg.get() + nx, nu * sizeof(double), hipMemcpyDeviceToHost));
+  return LLAMPC_OK;
+}
+
+int llampc_ctl_set_applied(llampc_ctl* c, const double* u0, const double* useq) {
+  if (!c || !u0) return fail(LLAMPC_E_ARG, "controller/u0 is NULL");
+  const int32_t H = c->cfg.H;
+  if (!ctl_applied_finite(u0, useq, H)) return fail(LLAMPC_E_ARG, "the applied input and sequence must be finite");
+  std::lock_guard<std::mutex> lc(c->mu);
+  if (c->pending) return fail(LLAMPC_E_STATE, "a controller tick is outstanding");
+  if (c->t < 1) return fail(LLAMPC_E_STATE, "no tick completed yet: there is no applied input to replace");
+  BankIdle idle(c->b);
+  if (idle.rc) return idle.rc;
+  hipStream_t s = c->b->stream;
+  // u_prev [2] and useq [HMAX][2] follow each other in CtlState: u0 | useq (or u0 again, row 0 alone)
+  static_assert(offsetof(CtlState, useq) == offsetof(CtlState, u_prev) + 2 * sizeof(double), "CtlState: u_prev, then useq");
+  double h[2 + 2 * LLAMPC_HMAX];
+  const size_t nd = useq ? 2 + 2 * (size_t)H : 4;
+  for (size_t i = 0; i < nd; ++i) h[i] = i < 2 ? u0[i] : useq ? useq[i - 2] : u0[i - 2];
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(reinterpret_cast<char*>(c->d_st.get()) + offsetof(CtlState, u_prev), h, nd * sizeof(double),
+                    hipMemcpyHostToDevice));
   return LLAMPC_OK;
 }
 

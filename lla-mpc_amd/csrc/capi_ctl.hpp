@@ -1,9 +1,11 @@
 // capi_ctl.hpp — what the controller's host units share (capi_ctl.hip: lifecycle, tick, wait, arming;
 // capi_ctl_shard.hip: the sharding transports; capi_ctl_corr.hip: the track and the corridor): the
 // handle, the view a tick takes of it (capi_host.hpp CtlView) and the cancel of its armed launch.
-// Included by those three units only.
+// Included by those three units and by the fused step's (capi_ctl_solve.hip), which enqueues the tick's
+// launch through ctl_tick_launched, declared at the end.
 #pragma once
 #include "capi_common.hpp"
+#include "ctl_solve_refuse.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -80,6 +82,10 @@ struct llampc_ctl {
   int32_t cor_nslots = 0;                //   and how many slots it rolled out
   // prepared ticks (capi_host.hpp CtlPrep): the armed launch, and the host transport's pending second launch
   llampc::CtlPrep arm, xg_second;
+  // a fused-step solver borrows this controller (llampc_ctl_solver_create; capi_ctl_solve.hip): the
+  // setters it rules out refuse while it is attached (ctl_solve_refuse.hpp ctl_solver_blocks)
+  bool solver_attached = false;
+  bool dbg_by_solver = false;            // d_dbg was allocated for the solver (freed when it goes)
   std::mutex mu;
 };
 
@@ -117,5 +123,12 @@ static inline void ctl_cancel(llampc_ctl* c) {
   c->armed = false;
   if (c->b && c->b->armed == c) c->b->armed = nullptr;
 }
+
+// A launched tick's steps as llampc_ctl_tick_async runs them (capi_ctl.hip), for the fused step, which
+// enqueues kernels of its own around the launch: refresh and prepare; then before(arg, warm) — the
+// prepared tick's warm flag; a non-zero return ends the call with nothing of the tick enqueued — then
+// the tick's one launch and its commit (the tick is then outstanding: llampc_ctl_wait).  The caller holds
+// c->mu and c->b->mu; the controller has no armed launch, exchange or gather transport.
+int ctl_tick_launched(llampc_ctl* c, const double* x_t, int (*before)(void* arg, int32_t warm), void* arg);
 
 #pragma GCC visibility pop

@@ -25,6 +25,7 @@ int llampc_ctl_set_track(llampc_ctl* c, const double* centre, const double* thet
 int llampc_ctl_set_corridor(llampc_ctl* c, double weight, double margin) {
   if (!c) return fail(LLAMPC_E_ARG, "controller is NULL");
   std::lock_guard<std::mutex> lc(c->mu);
+  if (const char* why = ctl_solver_blocks(c->solver_attached, CtlSetter::corridor, weight > 0)) return fail(LLAMPC_E_STATE, "%s", why);
   ctl_cancel(c);                         // as every other call: the tick after launches normally
   llampc_bank* b = c->b;
   const llampc_ctl_cfg& k = c->cfg;

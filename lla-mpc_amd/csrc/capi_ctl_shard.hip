@@ -39,6 +39,7 @@ int llampc_ctl_set_exchange(llampc_ctl* c, llampc_mailbox* mb, const double* gpa
   for (int g = 0; g < mb->world; ++g)
     if (!mb->box[g]) return fail(LLAMPC_E_STATE, "mailbox of peer %d not open", g);
   std::lock_guard<std::mutex> lc(c->mu);
+  if (const char* why = ctl_solver_blocks(c->solver_attached, CtlSetter::exchange, true)) return fail(LLAMPC_E_STATE, "%s", why);
   DeviceGuard g(b->device);
   DevBuf<double> gp;
   if (int rc = ctl_upload_global(c, c->xg_world ? "a gather transport" : nullptr, gparams, n_global, gp)) return rc;
@@ -62,6 +63,7 @@ int llampc_ctl_set_gather(llampc_ctl* c, int32_t world, int32_t rank, llampc_com
                 comm->rank, comm->world, comm->device, rank, world, b->device);
   if (int rc = ctl_check_global(b, n_global)) return rc;
   std::lock_guard<std::mutex> lc(c->mu);
+  if (const char* why = ctl_solver_blocks(c->solver_attached, CtlSetter::gather, true)) return fail(LLAMPC_E_STATE, "%s", why);
   DeviceGuard g(b->device);
   // everything into locals: a failed call leaves the controller as it was
   DevBuf<double> gp;

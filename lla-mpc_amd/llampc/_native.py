@@ -99,6 +99,13 @@ class CtlOut(C.Structure):
                 ("mu_used", C.c_double), ("scale_used", C.c_double), ("mu_pred", C.c_double),
                 ("dr_mean", C.c_double), ("df_mean", C.c_double), ("u_seq", (C.c_double * 2) * HMAX)]
 
+
+class CtlSolveOut(C.Structure):
+    """llampc_ctl_solve_out: the fused step's solve (llampc_ctl_step)."""
+    _fields_ = [("umpc", (C.c_double * 2) * HMAX), ("xmpc", (C.c_double * 6) * (HMAX + 1)), ("fval", C.c_double),
+                ("uprev", C.c_double * 2), ("model", C.c_int64), ("status", C.c_int32), ("committed", C.c_int32)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/llampc.h declares.
 _SIGNATURES = {
     "llampc_abi_version": (C.c_int32, []),
@@ -179,6 +186,12 @@ _SIGNATURES = {
     "llampc_ctl_reference": (C.c_int, [C.c_void_p, _dp, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                        _dp, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "llampc_ctl_destroy": (C.c_int, [C.c_void_p]),
+    # u0 [2], useq [H][2] or NULL
+    "llampc_ctl_set_applied": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "llampc_ctl_solver_create": (C.c_int, [C.c_void_p, C.POINTER(NlpCfg), C.POINTER(C.c_void_p)]),
+    # solver, x_t [6] -> llampc_ctl_out, llampc_ctl_solve_out
+    "llampc_ctl_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "llampc_ctl_solver_destroy": (C.c_int, [C.c_void_p]),
     "llampc_ctl_set_exchange": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_int64]),
     "llampc_ctl_set_gather": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _dp, C.c_int64]),
     "llampc_ctl_record_words": (C.c_int32, [C.c_int32]),

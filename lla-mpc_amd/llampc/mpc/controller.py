@@ -22,6 +22,12 @@ Host logic restated from the reference driver (llampc/mpc/run_nmpc_orca_llampc_r
                              enqueued during the previous tick and waits for x_t on a
                              doorbell, having done the look-back's RK4 step (it needs only the
                              state) — the tick rings it (llampc_ctl_set_prelaunch).
+  * ``LLAMPC.step``          device mode with ``solve=dict(...)``: the tick AND the NMPC solve of the
+                             model it selected (nlp_bank[current_model_idx].solve, rt.py:303-305) as
+                             one chain on the bank's stream (llampc_ctl_step); the solve's first input
+                             is the applied one, and the controller's state says so.
+  * ``LLAMPC.set_applied``   tells the controller which input was really applied after a tick, when
+                             it was not the tick's own (llampc_ctl_set_applied).
     mode="host":             the round-3 loop: host ConstantSpeed + host CandidateGenerator
                              around the fused plan launch, every (model, candidate) rolled out.
 """
@@ -211,6 +217,7 @@ class DeviceController:
         self.prelaunch = False
         self.corridor_weight, self.corridor_margin = 0.0, float(corridor_margin)
         self._has_track = False
+        self._solver = None
         if float(corridor_weight) > 0:
             self.set_corridor(corridor_weight, corridor_margin)
         if prelaunch:
@@ -255,6 +262,59 @@ class DeviceController:
         n = nat.C.c_int32()
         nat.check(nat.load().llampc_ctl_corridor_costs(self._h, nat.dptr(out), nat.C.byref(n)))
         return out[:n.value].copy()
+
+    def attach_solver(self, samples=1024, iters=8, elite=32, sigma=(0.3, 0.15), std_floor=1e-4, seed=0):
+        """The fused step's solver (llampc_ctl_solver_create): the cross-entropy NMPC search of
+        setupNLP with the controller's own cost, bounds, rate bounds, H and Ts.  Refused (NativeError,
+        E_STATE) with prelaunch on, a sharded exchange or a corridor weight > 0; while it is attached
+        those setters are refused in turn.  One per controller."""
+        if self._solver is not None:
+            raise nat.NativeError("the controller already has a solver", nat.E_STATE)
+        cfg = nat.NlpCfg()
+        cfg.H, cfg.samples, cfg.iters, cfg.elite = self.H, int(samples), int(iters), int(elite)
+        cfg.Ts, cfg.std_floor, cfg.seed = float(self.cfg.Ts), float(std_floor), int(seed)
+        cfg.sigma0[0], cfg.sigma0[1] = float(sigma[0]), float(sigma[1])
+        cfg.cost = self.cfg.cost
+        for j in range(2):                   # the tick's rate bound, as setupNLP's chain takes it
+            m = float(self.cfg.cost.rate_max[j])
+            cfg.rate_lo[j], cfg.rate_hi[j] = (1.0, -1.0) if m < 0 else (-m * cfg.Ts, m * cfg.Ts)
+        h = nat.C.c_void_p()
+        nat.check(nat.load().llampc_ctl_solver_create(self._h, nat.C.byref(cfg), nat.C.byref(h)))
+        self._solver, self.solve_cfg = h, cfg
+        self._f_step = nat.load().llampc_ctl_step
+
+    def detach_solver(self):
+        """Destroys the fused step's solver; the controller ticks on as one that never had it."""
+        if getattr(self, "_solver", None) is not None:
+            nat.load().llampc_ctl_solver_destroy(self._solver)
+            self._solver = None
+
+    def step(self, x_t, out=None, sol=None):
+        """One fused step (llampc_ctl_step), blocking: the tick's record and the solve's
+        (CtlOut, CtlSolveOut), filled and returned (new ones if None)."""
+        if self._solver is None:
+            raise nat.NativeError("step() needs a solver (attach_solver / LLAMPC(solve=...))", nat.E_STATE)
+        out = nat.CtlOut() if out is None else out
+        sol = nat.CtlSolveOut() if sol is None else sol
+        self._x[:] = x_t
+        rc = self._f_step(self._solver, self._xp, nat.C.addressof(out), nat.C.addressof(sol))
+        if rc:
+            nat.check(rc)
+        return out, sol
+
+    def set_applied(self, u0, u_seq=None):
+        """The input really applied after the last tick (llampc_ctl_set_applied): u0 [2] becomes the
+        state's u_{t-1}; u_seq [2, H] (or None: the chosen sequence with its first column replaced by
+        u0) the next candidates' base.  The next tick's look-back transition, du_0 and candidates use
+        them; the past record stays."""
+        u0 = nat.f64(np.asarray(u0, dtype=np.float64).reshape(2))
+        seq = None
+        if u_seq is not None:
+            u_seq = np.asarray(u_seq, dtype=np.float64)
+            if u_seq.shape != (2, self.H):
+                raise ValueError(f"u_seq must be [2, {self.H}], got {u_seq.shape}")
+            seq = np.ascontiguousarray(u_seq.T)
+        nat.check(nat.load().llampc_ctl_set_applied(self._h, u0.ctypes.data, None if seq is None else seq.ctypes.data))
 
     def set_prelaunch(self, on=True):
         """Arm every next tick (llampc_ctl_set_prelaunch): its launch is enqueued behind the
@@ -353,6 +413,7 @@ class DeviceController:
         return xref, pj.value, vr.value
 
     def close(self):
+        self.detach_solver()                 # it borrows the controller: first
         if getattr(self, "_h", None) is not None:
             nat.load().llampc_ctl_destroy(self._h)
             self._h = None
@@ -421,6 +482,44 @@ class CtlResult:
         return (p.la_best_model, p.la_best_cand, p.la_best_cost)
 
 
+class StepResult:
+    """A fused step's result (LLAMPC.step): ``tick`` the CtlResult as tick() returns it; the solve's
+    ``umpc`` [2, H], ``fval``, ``xmpc`` [6, H+1]; ``solved`` (a finite objective was found) and
+    ``committed`` (umpc is now the controller's applied sequence); ``model`` the global index solved
+    with (-1: the nominal model, while warm); ``uprev`` the solve's du_0 reference; ``u0`` the applied
+    input: umpc[:, 0] if committed, else the tick's own."""
+    __slots__ = ("tick", "raw", "H", "fval", "solved", "committed", "model", "status", "_u", "_x")
+
+    def __init__(self, tick: CtlResult, s: "nat.CtlSolveOut", H: int):
+        self.tick, self.raw, self.H = tick, s, int(H)
+        self.fval, self.status, self.model = s.fval, s.status, s.model
+        self.solved, self.committed = s.status == nat.NLP_OK, bool(s.committed)
+        self._u = self._x = None
+
+    @property
+    def umpc(self):
+        if self._u is None:
+            self._u = np.frombuffer(self.raw.umpc, np.float64, count=2 * self.H).reshape(self.H, 2).T
+        return self._u
+
+    @property
+    def xmpc(self):
+        if self._x is None:
+            self._x = np.frombuffer(self.raw.xmpc, np.float64, count=6 * (self.H + 1)).reshape(self.H + 1, 6).T
+        return self._x
+
+    @property
+    def uprev(self):
+        return np.array([self.raw.uprev[0], self.raw.uprev[1]])
+
+    @property
+    def u0(self):
+        if self.committed:
+            r = self.raw.umpc[0]
+            return (r[0], r[1])
+        return self.tick.u0
+
+
 def result_from_ctl(o: "nat.CtlOut", H: int) -> CtlResult:
     """The result of a controller tick: the record plus the chosen sequence [2, H]."""
     return CtlResult(o, H)
@@ -431,15 +530,27 @@ class LLAMPC:
 
     ``nominal``: the Pacejka parameters the warm-up ticks plan with (default ORCA(),
     the reference's true_model / params at setup, rt.py:78-79, 207).  ``prelaunch``: device
-    mode's armed ticks (module docstring); results are those of launched ticks."""
+    mode's armed ticks (module docstring); results are those of launched ticks.  ``solve``: device
+    mode only, a dict of the NMPC search's parameters (samples=1024, iters=8, elite=32,
+    sigma=(0.3, 0.15), std_floor=1e-4, seed=0; the cost, bounds, H and Ts are the controller's):
+    ``step()`` then runs the tick and the selected model's solve as one chain.  It forces
+    ``prelaunch`` off (the fused step has no armed launches), and ``set_prelaunch(True)`` raises."""
 
     def __init__(self, bank: ModelBank, track, H=20, Ts=0.02, K=10, C=64, v_factor=0.9,
                  mu_init=1.0, S=20, alpha=0.08, cost=None, integrator="rk4", seed=2,
                  nan_policy=nat.NAN_FIRST, nominal: dict | None = None, mode="device",
-                 sigma=(0.05, 0.02), debug_inputs=False, prelaunch=True, corridor_weight=0.0, corridor_margin=0.0):
+                 sigma=(0.05, 0.02), debug_inputs=False, prelaunch=True, corridor_weight=0.0, corridor_margin=0.0,
+                 solve: dict | None = None):
         from llampc.params import ORCA
         if mode not in ("device", "host"):
             raise ValueError(f"mode={mode!r}: 'device' or 'host'")
+        if solve is not None:
+            if mode != "device":
+                raise ValueError("solve=... needs mode='device' (the solve is chained behind the tick's launch)")
+            unknown = set(solve) - {"samples", "iters", "elite", "sigma", "std_floor", "seed"}
+            if unknown:
+                raise ValueError(f"solve: unknown keys {sorted(unknown)}")
+            prelaunch = False                # the fused step has no armed launches
         check_corridor_args(track, corridor_weight, corridor_margin)
         if float(corridor_weight) > 0 and mode != "device":
             raise ValueError("corridor_weight needs mode='device' (the corridor is built inside the tick's launch)")
@@ -476,6 +587,8 @@ class LLAMPC:
                     self._ctl.set_prelaunch(True)
             elif prelaunch:
                 self._ctl.set_prelaunch(True)
+            if solve is not None:
+                self._ctl.attach_solver(**solve)
         else:
             # a one-model bank: the warm-up look-ahead runs the same kernel on the nominal model
             self.nominal_bank = ModelBank(col, shared=bank.shared, W=1, device=bank.device)
@@ -489,7 +602,7 @@ class LLAMPC:
         # 64-bit), so device mode accepts the seeds the host sampler cannot take and then has none
         self.gen = CandidateGenerator(C, H, Ts, seed=seed) if mode == "host" or 0 <= int(seed) < 2 ** 32 else None
         self.nan_policy = nan_policy
-        self._last = self._last_full = None
+        self._last = self._last_full = self._applied = None
         self._u_seq_host = self._u_prev_host = self._topk_host = None
         self.current_model = 0          # rt.py:264
         self.projidx = 0
@@ -612,6 +725,50 @@ class LLAMPC:
         self.t += 1
         return res
 
+    def step(self, x_t) -> StepResult:
+        """Device mode with ``solve=``: one fused step (llampc_ctl_step) — the tick, the NMPC solve of
+        the model it selected (the nominal one while the window fills) warm-started from the tick's
+        chosen sequence, and the commit of its solution as the applied sequence, enqueued back to back
+        with one host wait.  A solve without a finite objective commits nothing: the tick's candidate
+        is then the applied input (``StepResult.u0`` says which)."""
+        if self._ctl is None or self._ctl._solver is None:
+            raise nat.NativeError("step() needs mode='device' and solve=dict(...)", nat.E_STATE)
+        self._usable()
+        x_t = np.asarray(x_t, dtype=np.float64)
+
+        def run():
+            o, s = self._ctl.step(x_t)
+            res = StepResult(self._finish_device(o, x_t), s, self.H)
+            if res.committed:
+                self._applied = (np.array(res.u0), res.umpc.T.copy())
+            return res
+        return self._guarded(run)
+
+    def close_solver(self):
+        """Gives up the fused step (DeviceController.detach_solver): ``tick()`` goes on as on a
+        controller that never had a solver (prelaunch stays off until set_prelaunch(True))."""
+        if self._ctl is not None:
+            self._ctl.detach_solver()
+
+    def set_applied(self, u0, u_seq=None):
+        """Device mode, after a tick: the input really applied was ``u0`` [2], not the tick's own
+        u_seq[:, 0] — an external solve's (pass its ``u_seq`` [2, H] too: the next candidates are then
+        drawn around it) or a safety override's (DeviceController.set_applied).  The next tick's
+        look-back scores the bank on the transition under ``u0``."""
+        if self._ctl is None:
+            raise nat.NativeError("set_applied() needs mode='device'", nat.E_STATE)
+        self._usable()
+        if self._last is None:
+            raise nat.NativeError("set_applied(): no tick completed yet", nat.E_STATE)
+        self._ctl.set_applied(u0, u_seq)
+        u0 = np.asarray(u0, dtype=np.float64).reshape(2).copy()
+        if u_seq is None:
+            seq = self._last.u_seq.T.copy()
+            seq[0] = u0
+        else:
+            seq = np.asarray(u_seq, dtype=np.float64).T.copy()
+        self._applied = (u0, seq)
+
     def tick_begin(self, x_t):
         """Device mode: enqueue the tick (llampc_ctl_tick_async) and return at once, so the
         controllers of several banks (e.g. two tracks) run concurrently; tick_end() completes it."""
@@ -664,16 +821,19 @@ class LLAMPC:
         self.current_model = res.best_model
         self.projidx = o.projidx
         self._last = res
+        self._applied = None                 # until step() commits or set_applied() says otherwise
         self.x_prev = x_t
         self.t += 1
         return res
 
-    # device mode keeps the last result; these read it on demand
+    # device mode keeps the last result (and what was applied in its place); these read them on demand
     last_topk = property(lambda self: self._last_full.topk if self._last_full is not None else self._topk_host,
                          lambda self, v: setattr(self, "_topk_host", v))
-    u_seq = property(lambda self: self._last.u_seq.T if self._last is not None else self._u_seq_host,
+    u_seq = property(lambda self: self._applied[1] if self._applied is not None
+                     else self._last.u_seq.T if self._last is not None else self._u_seq_host,
                      lambda self, v: setattr(self, "_u_seq_host", v))
-    u_prev = property(lambda self: self._last.u_seq[:, 0].copy() if self._last is not None else self._u_prev_host,
+    u_prev = property(lambda self: self._applied[0].copy() if self._applied is not None
+                      else self._last.u_seq[:, 0].copy() if self._last is not None else self._u_prev_host,
                       lambda self, v: setattr(self, "_u_prev_host", v))
 
     def inputs(self):
